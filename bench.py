@@ -16,8 +16,14 @@ Scaling modes (--scaling):
 Placement (pods placed/s) runs over the same global node set: one GPU, or dist.place_sharded with
 the snapshot replicated and the tile range sharded.
 
-  python bench.py [--gpus N --steps K --warmup W] [--scaling strong|config4|weak]
+  python bench.py [--gpus N --steps K --warmup W] [--scaling strong|config4|weak] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline rate, ms_per_step and
+what the timed steps themselves yield (HIP-event kernel time, engine counters).  --dump-outputs DIR also writes
+what the last timed step computed as DIR/<name>.npy (dump_outputs).  --full adds every other section, each a run
+of its own: host_outputs, placement, the CPU baselines, dropin_cycle, config2_distinct, config3, config5, la_extra;
+the --no-* and --c*-pods options select among them.
 """
 from __future__ import annotations
 
@@ -52,6 +58,11 @@ def parse():
                     help="torch.distributed backend (gloo: CPU rehearsal of N > 1); loopback: gloo for the matrix-mode "
                          "merge and kg_place_sharded's native loop over the host shared-memory communicator "
                          "(kg_comm_init_loopback), so N ranks can share one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other section (host outputs, placement, CPU baselines, "
+                         "drop-in cycle, distinct pods, config 3, config 5, LoadAware extra resources)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--no-placement", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-distinct", action="store_true", help="skip the config2_distinct section")
@@ -69,7 +80,10 @@ def parse():
                     help="one-pod scheduling cycles through the C-ABI (kg_pods_set, kg_eval to host, kg_commit); 0 skips")
     ap.add_argument("--la-extra-pods", type=int, default=1_000,
                     help="matrix-mode pods with LoadAware resourceWeights beyond cpu / memory (k_eval_exact); 0 skips")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def pmc_traffic(kernel_prefix: str = "k_eval"):
@@ -128,6 +142,43 @@ def cpu_median(run, cap, target_s=2.0, runs=5, start=4):
         run(k)
         ts.append(time.perf_counter() - t0)
     return k, float(np.median(ts)), [round(t, 3) for t in ts]
+
+
+DUMP_SAMPLE_BYTES = 48 << 20   # budget of the two sampled planes of dump_outputs (everything it writes < 64 MB)
+
+
+def dump_outputs(out_dir, engine, mask, scores, merged, N):
+    """--dump-outputs: what the last timed step left in the caller's buffers, as float arrays two builds can be
+    compared by.  Over every pod: the merged top-1 key decoded (top1_node, top1_score: −1 = no feasible node), the
+    number of feasible nodes (feasible_nodes) and the sum of each score plane over this rank's nodes (score_sums:
+    [P][2] = Fit, LoadAware).  Over a fixed, seeded sample of pod rows, every node of this rank: the feasibility
+    bits unpacked (mask_sample: [S][N] 0 / 1) and both u8 score planes (scores_sample: [S][N][2]); sample_pods
+    holds the sampled pod indices."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    P, W = mask.shape
+    node, total = engine.decode_top1(merged.cpu().numpy().view(np.uint64))
+    arrays = {"top1_node": node.astype(np.float64), "top1_score": total.astype(np.float64)}
+    # feasible nodes per pod: popcount of the mask words (bits past N in the last word left out), 1024 pods at a time
+    lut = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int64, device=mask.device)
+    tail = N - 64 * (W - 1)
+    counts = torch.empty(P, dtype=torch.int64, device=mask.device)
+    for p0 in range(0, P, 1024):
+        m = mask[p0:p0 + 1024].clone()
+        if tail < 64:
+            m[:, -1] &= (1 << tail) - 1
+        counts[p0:p0 + 1024] = lut[m.view(torch.uint8).long()].sum(dim=1)
+    arrays["feasible_nodes"] = counts.cpu().numpy().astype(np.float64)
+    arrays["score_sums"] = scores[:, :N, :].sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64)
+    S = int(max(1, min(P, DUMP_SAMPLE_BYTES // (12 * N))))
+    pods = np.sort(np.random.default_rng(20240607).choice(P, size=S, replace=False))
+    idx = torch.from_numpy(pods).to(mask.device)
+    arrays["sample_pods"] = pods.astype(np.float64)
+    arrays["mask_sample"] = engine.unpack_mask(mask[idx].cpu().numpy().view(np.uint64), N).astype(np.float32)
+    arrays["scores_sample"] = scores[idx][:, :N, :].cpu().numpy().astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def bench_config3(args, engine, synth, shipped_profile, dev, stream, cpu_model):
@@ -634,13 +685,18 @@ def main():
     algo_bytes = P * N * BYTES_PER_PAIR + N * BYTES_PER_NODE + P * BYTES_PER_POD
     achieved = algo_bytes / (k_ms * 1e-3)
     feasible_pods = int((merged != 0).sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine, mask, scores, merged, N)
 
+    full = args.full   # every section below is a run of its own beside the timed steps
     host_out = None   # before placement: the same snapshot as the timed steps
-    if not args.no_host_outputs and world == 1:
+    if full and not args.no_host_outputs and world == 1:
         host_out = bench_host_outputs(args, engine, eng, P, N, now, dev)
 
     placement = None
-    if not args.no_placement and world == 1:
+    if not full or args.no_placement:
+        pass
+    elif world == 1:
         eng.load_snapshot(node_rows)
         torch.cuda.synchronize(dev)
         tp0 = time.perf_counter()
@@ -649,7 +705,7 @@ def main():
         placement = {"pods": P, "nodes": N, "seconds": round(tp1 - tp0, 6),
                      "pods_placed_per_s": round(P / (tp1 - tp0), 1), "placed": int((nodes >= 0).sum()),
                      "chunk": int(cfg["place_chunk"]), "mode": "kg_place, one GPU"}
-    elif not args.no_placement:
+    else:
         # node-sharded sequential cycle over the union of every rank's shard (replicated snapshot,
         # per-tile partial keys merged with RCCL all_reduce(MAX), replicated resolve: koordinator_amd/dist.py)
         from koordinator_amd import dist as kdist
@@ -678,7 +734,7 @@ def main():
                               else f"dist.place_sharded over {world} ranks ({args.backend})")}
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle  # CPU restatement, timed as the baseline only
         workers = min(16, os.cpu_count() or 1)
         k, med, ts = cpu_median(lambda k: oracle.eval_parallel(cfg, cl, np.arange(k), now, workers), P,
@@ -718,19 +774,19 @@ def main():
                                       "sample": "the oracle's sequential cycle per pod (placement.cpu_baseline.sequential)"}
 
     distinct = None
-    if not args.no_distinct and world == 1:
+    if full and not args.no_distinct and world == 1:
         distinct = bench_config2_distinct(args, engine, synth, cfg, node_rows, N, now, dev, stream)
 
     config3 = None
-    if args.c3_pods > 0 and world == 1:
+    if full and args.c3_pods > 0 and world == 1:
         config3 = bench_config3(args, engine, synth, shipped_profile, dev, stream, cpu_model)
 
     config5 = None
-    if args.c5_pods > 0 and world == 1:
+    if full and args.c5_pods > 0 and world == 1:
         config5 = bench_config5(args, engine, synth, shipped_profile, dev, stream, cpu_model)
 
     la_extra = None
-    if args.la_extra_pods > 0 and world == 1:
+    if full and args.la_extra_pods > 0 and world == 1:
         la_extra = bench_la_extra(args, engine, synth, shipped_profile, dev, stream)
 
     # the committed PMC passes profile the default workload (tools/profile.sh: config 2, one GPU)

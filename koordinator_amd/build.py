@@ -83,19 +83,28 @@ def build_variant(tag: str, defines: list) -> str:
     return so
 
 
-def build_bounds(force: bool = False) -> str:
-    """The bounds-checked engine (-DKG_BOUNDS_CHECK): every index into the pipelined placement's shared buffers is
-    checked on the device and a violation is reported by the next kg_place / kg_eval instead of faulting.  A debug
-    library beside the product one (loaded through KG_ENGINE_SO by tests/test_bounds_gpu.py); not built by default."""
-    if not force and not _newer(BOUNDS_SO, engine_sources()):
-        return BOUNDS_SO
+def _bounds_object() -> str:
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     obj_dir = os.path.join(LIB_DIR, "obj")
+    os.makedirs(obj_dir, exist_ok=True)
     common = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
     dev_obj = os.path.join(obj_dir, "kg_engine_bounds.o")
     _run([hipcc, *common, "-DKG_BOUNDS_CHECK", f"--offload-arch={ARCH}", "-c", os.path.join(CSRC, "kg_engine.hip"),
           "-o", dev_obj])
-    objs = [os.path.join(obj_dir, n) for n in ("kg_host.o", "kg_cpuset.o", "kg_comm.o")]
+    return dev_obj
+
+
+def build_bounds(force: bool = False, dev_obj: str | None = None) -> str:
+    """The bounds-checked engine (-DKG_BOUNDS_CHECK): every index into the pipelined placement's shared buffers is
+    checked on the device and a violation is reported by the next kg_place / kg_eval instead of faulting.  A debug
+    library beside the product one (loaded through KG_ENGINE_SO by tests/test_bounds_gpu.py, never by the product).
+    `dev_obj`: its device object, already compiled (build_all compiles it beside the product's)."""
+    if dev_obj is None:
+        if not force and not _newer(BOUNDS_SO, engine_sources()):
+            return BOUNDS_SO
+        dev_obj = _bounds_object()
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    objs = [os.path.join(LIB_DIR, "obj", n) for n in ("kg_host.o", "kg_cpuset.o", "kg_comm.o")]
     if not all(os.path.exists(o) for o in objs):
         raise RuntimeError("build the product engine first (its host objects are linked into the bounds build)")
     tmp = BOUNDS_SO + ".tmp"
@@ -144,8 +153,17 @@ def build_sanitized(force: bool = False) -> tuple[str, str]:
 
 
 def build_all(force: bool = False) -> None:
+    """The oracle, the engine and the bounds-checked engine the GPU suite compares it with; the two device
+    objects (minutes each) are compiled side by side."""
+    from concurrent.futures import ThreadPoolExecutor
+
     build_oracle(force)
-    build_engine(force)
+    stale = force or _newer(BOUNDS_SO, engine_sources())
+    with ThreadPoolExecutor(1) as pool:
+        dev_obj = pool.submit(_bounds_object) if stale else None
+        build_engine(force)
+        if dev_obj is not None:
+            build_bounds(dev_obj=dev_obj.result())
 
 
 if __name__ == "__main__":

@@ -318,7 +318,7 @@ def test_bench_spawns_ranks_for_gpus_flag():
     import sys
 
     root = os.path.dirname(HERE)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--full",
                           "--pods", "256", "--nodes", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                           "--c3-pods", "0", "--c5-pods", "0"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-4000:]
