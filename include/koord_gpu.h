@@ -27,6 +27,8 @@
  *                           Reserve) for a queue of pods, with Reserve deltas of LoadAware.Reserve
  *                           (load_aware.go:260-267) and NodeInfo.AddPod (mirror reservation/transformer.go:293-306)
  *   kg_commit               one Reserve (AssumePod + LoadAware.Reserve) of a pod on a node
+ *   kg_cycle_one            one pass of upstream scheduleOne for one pod in one launch: Filter + Score over every
+ *                           node, selectHost, and (KG_CYCLE_COMMIT) the Reserve of the chosen node
  *   kg_rsv_set              reservation cache feed (reservation/cache.go:249-269 forEachAvailableReservationOnNode,
  *                           frameworkext/reservation_info.go:200-300): per-node reservation slots for the
  *                           Reservation plugin's restore / Filter / Score / Reserve (reservation/transformer.go:49-291,
@@ -53,7 +55,7 @@
 extern "C" {
 #endif
 
-#define KG_ABI_VERSION 12
+#define KG_ABI_VERSION 13
 #define KG_QUOTA_MAX_DEPTH 64 /* longest kg_quota parent chain (cycles are rejected) */
 
 /* largest kg_config.place_chunk / kg_place_chunk_resolve chunk (the resolve kernel's touched list) */
@@ -547,7 +549,8 @@ enum kg_struct_id {
     KG_SID_RESOURCE_LIST = 0, KG_SID_CONFIG, KG_SID_CONTAINER, KG_SID_POD_SPEC,
     KG_SID_AGGREGATED_USAGE, KG_SID_POD_METRIC, KG_SID_ASSIGNED_POD, KG_SID_NODE_SPEC,
     KG_SID_CLUSTER_VIEW, KG_SID_POD_ROW, KG_SID_NODE_ROW, KG_SID_EVAL_OUT, KG_SID_NUMA_SPEC,
-    KG_SID_RESERVATION, KG_SID_QUOTA, KG_SID_RSV_RESTORED, KG_SID_CPU_INFO, KG_SID_COUNTERS, KG_SID_COUNT
+    KG_SID_RESERVATION, KG_SID_QUOTA, KG_SID_RSV_RESTORED, KG_SID_CPU_INFO, KG_SID_COUNTERS, KG_SID_CYCLE_OUT,
+    KG_SID_COUNT
 };
 int64_t kg_struct_size(int32_t sid);
 
@@ -626,7 +629,7 @@ kg_status kg_snapshot_remove(kg_engine *eng, int32_t node_index);
 kg_status kg_snapshot_download(kg_engine *eng, int32_t first, int32_t n, kg_node_row *out);
 /* Snapshot generation (SURVEY §5 error contract; replaces the Go cache's generation check in
  * Cache.UpdateSnapshot, a per-cycle staleness test): the count of successful snapshot mutations —
- * kg_snapshot_reset, kg_snapshot_upsert / _remove, kg_commit and each placement resolve (kg_place,
+ * kg_snapshot_reset, kg_snapshot_upsert / _remove, kg_commit, a committing kg_cycle_one and each placement resolve (kg_place,
  * kg_place_chunk_resolve).  After a HIP error the device state is stale: this returns KG_ERR_STATE (with
  * the generation reached), every other entry point fails with KG_ERR_STATE, and the caller falls back to
  * the CPU plugins until kg_snapshot_reset + upsert reload the snapshot. */
@@ -761,6 +764,31 @@ kg_status kg_quota_download(kg_engine *eng, kg_quota *out, int32_t n);
 /* Single Reserve on the device snapshot (pod = index in the uploaded batch); a cpuset pod takes its CPUs
  * from the node's kg_cpus_set table.  KG_NOT_FOUND ⇔ its Allocate fails (nothing changed). */
 kg_status kg_commit(kg_engine *eng, int32_t pod, int32_t node);
+
+/* One scheduling cycle of one pod (upstream scheduleOne: Filter and Score over every node of the shard,
+ * selectHost, Reserve) as ONE kernel launch and ONE stream synchronisation: the per-pod loop of the Go plugins
+ * without kg_pods_set + kg_eval + kg_commit.  The pod row travels with the launch; the batch uploaded with
+ * kg_pods_set is neither read nor replaced.
+ * Selection is exactly kg_pods_set(pod, 1) + kg_eval(top1): the shard of kg_set_shard, ties to the lowest node
+ * index, the exact int64 pair path for nodes outside the fp64 bounds, for the later named slots and for LoadAware
+ * weights beyond cpu / memory.  With KG_CYCLE_COMMIT the chosen node is reserved in the same launch exactly as
+ * kg_commit(pod, node) would (snapshot generation + 1, kg_counters.placed + 1); without a feasible node nothing
+ * changes.
+ * planes (may be NULL): mask / scores / numa_scores receive the pod's planes in kg_eval's P = 1 layout (host or
+ * device pointers by out_on_device), top1 the key; rsv_scores must be NULL.  They describe the snapshot before
+ * the commit.
+ * KG_ERR_UNSUPPORTED (nothing launched, nothing changed) — keep the three-call path — when Reservation is enabled
+ * with reservation slots loaded, when ElasticQuota is enabled, and under NodeNUMAResource for a pod that binds a
+ * cpuset (KG_POD_NUMA_CPU_BIND) or a snapshot holding a node with a CPU bind policy. */
+#define KG_CYCLE_COMMIT 0x1u       /* Reserve the chosen node in the same launch */
+typedef struct kg_cycle_out {
+    uint64_t key;        /* as kg_eval_out.top1: (total+1) << 32 | (0xFFFFFFFF - node); 0 <=> no feasible node */
+    int32_t  node;       /* chosen node (global index), -1 when none */
+    int32_t  committed;  /* 1 <=> the Reserve was applied to the snapshot */
+    int64_t  score;      /* total score, -1 when none (kg_place's out_score convention) */
+} kg_cycle_out;
+kg_status kg_cycle_one(kg_engine *eng, const kg_pod_row *pod, int64_t now_ns, uint32_t flags,
+                       const kg_eval_out *planes /* may be NULL */, kg_cycle_out *out);
 
 /* Measurement: when on, every k_eval launch (kg_eval, kg_place_chunk_eval) is bracketed by a
  * pair of HIP events on the engine stream (ring of 256).  kg_eval_kernel_times writes the

@@ -15,7 +15,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ENGINE_SO = os.environ.get("KG_ENGINE_SO") or os.path.join(_HERE, "lib", "libkoordgpu.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 COMM_ID_BYTES = 128   # KG_COMM_ID_BYTES
 COMM_NONE, COMM_RCCL, COMM_LOOPBACK = 0, 1, 2   # kg_comm_kind
 # kg_set_forms bits (include/koord_gpu.h)
@@ -50,6 +50,7 @@ CPU_EXCL_UNSET, CPU_EXCL_NONE, CPU_EXCL_PCPU_LEVEL, CPU_EXCL_NUMA_NODE_LEVEL = r
 NODE_CPU_BIND_NONE, NODE_CPU_BIND_FULL_PCPUS_ONLY, NODE_CPU_BIND_SPREAD_BY_PCPUS = range(3)
 NUMA_ALLOC_DEFAULT, NUMA_ALLOC_MOST, NUMA_ALLOC_LEAST, NUMA_ALLOC_DISTRIBUTE_EVENLY = range(4)
 NOT_FOUND = 1   # KG_NOT_FOUND
+CYCLE_COMMIT = 0x1   # KG_CYCLE_COMMIT: kg_cycle_one reserves the chosen node in the same launch
 NODE_VALID, NODE_HAS_METRIC, NODE_HAS_UPDATE_TIME, NODE_LA_PASS_NONPROD, NODE_LA_PASS_PROD = 0x1, 0x2, 0x4, 0x8, 0x10
 NODE_NUMA_OPTIONS, NODE_NUMA_TOPO_VALID, NODE_NUMA_TOPO_INVALID = 0x40, 0x80, 0x100
 
@@ -158,8 +159,11 @@ RSV_RESTORED = np.dtype([
 COUNTERS = np.dtype([(k, "<u8") for k in ("eval_calls", "evals", "out_bytes", "resolved", "placed", "h2d_bytes",
                                             "timed_launches", "kernel_ns")])
 
+CYCLE_OUT = np.dtype([("key", "<u8"), ("node", "<i4"), ("committed", "<i4"), ("score", "<i8")], align=True)
+
 STRUCT_IDS = [RESOURCE_LIST, CONFIG, CONTAINER, POD_SPEC, AGGREGATED_USAGE, POD_METRIC, ASSIGNED_POD, NODE_SPEC,
-              None, POD_ROW, NODE_ROW, None, NUMA_SPEC, RESERVATION, QUOTA, RSV_RESTORED, CPU_INFO, COUNTERS]
+              None, POD_ROW, NODE_ROW, None, NUMA_SPEC, RESERVATION, QUOTA, RSV_RESTORED, CPU_INFO, COUNTERS, CYCLE_OUT]
+SID_CYCLE_OUT = len(STRUCT_IDS) - 1   # KG_SID_CYCLE_OUT
 
 
 class ClusterView(ctypes.Structure):
@@ -181,6 +185,12 @@ class EvalOut(ctypes.Structure):
     _fields_ = [("mask", ctypes.c_void_p), ("scores", ctypes.c_void_p), ("top1", ctypes.c_void_p),
                 ("out_on_device", ctypes.c_int32), ("_pad", ctypes.c_int32), ("numa_scores", ctypes.c_void_p),
                 ("rsv_scores", ctypes.c_void_p)]
+
+
+class CycleOut(ctypes.Structure):
+    """kg_cycle_out: the result of kg_cycle_one."""
+    _fields_ = [("key", ctypes.c_uint64), ("node", ctypes.c_int32), ("committed", ctypes.c_int32),
+                ("score", ctypes.c_int64)]
 
 
 def ptr(a) -> ctypes.c_void_p:
@@ -224,6 +234,7 @@ EXPORTED = [
     "kg_snapshot_generation", "kg_cpuset_take", "kg_row_reserve", "kg_cpus_set", "kg_cpus_download",
     "kg_place_chunk_resolve_prev", "kg_set_eval_stream", "kg_set_forms", "kg_comm_unique_id", "kg_comm_init",
     "kg_place_sharded", "kg_counters_get", "kg_counters_reset", "kg_comm_init_loopback", "kg_comm_kind",
+    "kg_cycle_one",
 ]
 
 _lib = None
@@ -274,6 +285,7 @@ def lib() -> ctypes.CDLL:
         "kg_comm_unique_id": (i32, [vp]), "kg_comm_init": (i32, [vp, i32, i32, vp]),
         "kg_place_sharded": (i32, [vp, ctypes.c_int64, vp, vp]), "kg_counters_get": (i32, [vp, vp]), "kg_counters_reset": (i32, [vp]),
         "kg_comm_init_loopback": (i32, [vp, i32, i32, ctypes.c_char_p]), "kg_comm_kind": (i32, [vp]),
+        "kg_cycle_one": (i32, [vp, vp, i64, ctypes.c_uint32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if host_only and not hasattr(L, name):
@@ -298,3 +310,5 @@ def check_abi(L=None) -> None:
             raise RuntimeError(f"struct id {sid}: C size {got} != numpy {dt.itemsize}")
     if L.kg_struct_size(8) != ctypes.sizeof(ClusterView) or L.kg_struct_size(11) != ctypes.sizeof(EvalOut):
         raise RuntimeError("view/eval_out struct size mismatch")
+    if L.kg_struct_size(SID_CYCLE_OUT) != ctypes.sizeof(CycleOut) or CYCLE_OUT.itemsize != ctypes.sizeof(CycleOut):
+        raise RuntimeError("cycle_out struct size mismatch")

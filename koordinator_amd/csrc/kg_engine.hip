@@ -33,6 +33,7 @@
 #include <unordered_map>
 #include <utility>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kg_comm.h"
@@ -2874,6 +2875,124 @@ __global__ void k_commit_one(kg_consts c, kg_planes pl, const kg_pod_dev *__rest
 }
 
 // ---------------------------------------------------------------------------------------
+// kg_cycle_one: the scheduling cycle of ONE pod (Filter + Score over the shard, selectHost, Reserve) in one launch
+// ---------------------------------------------------------------------------------------
+// One node per thread, 256 threads per workgroup, the pod row in the kernel arguments (wave-uniform: scalar loads).
+// Per pair the resolve's own code (load_node, eval_pair, kg_numa_eval_any: what pair_key runs), restricted to the
+// planes the pod compares or scores.  The workgroup's best key (DPP wave max, LDS across the four waves) goes into
+// one engine-owned word with an agent-scope atomic max; then the workgroup releases (agent scope) and draws a
+// ticket.  The workgroup that draws the last ticket acquires, takes the word with an agent-scope atomic exchange
+// (the per-XCD L2s are not coherent: never a plain load), and one thread of it decodes the winner, runs the Reserve
+// of k_commit_one on the winner's row and planes, writes the result to pinned host memory and leaves key and ticket
+// at 0 for the next call.  Every other workgroup read its rows before it drew its ticket, and the last arriver
+// writes only after it has seen every ticket, so no read of this launch can meet the commit's writes; the next
+// launch is ordered behind them by the kernel boundary.
+// NUMA: the instantiation of an engine with NodeNUMAResource (the plain one carries no NUMA code: its hint
+// enumeration and Reserve are calls, which would charge the plain form their register budget); the pod row then
+// sits in LDS, because the out-of-line NUMA code takes it by address.
+// PLANES: the pod's kg_eval planes (P = 1 layout) beside the key: the wave's ballot is its mask word, each thread
+// stores its u16 {fit, la} and its u8 NodeNUMAResource score.
+typedef __attribute__((address_space(1))) unsigned long long kg_gu64;
+typedef __attribute__((address_space(1))) uint32_t kg_gu32;
+struct CycleArgs {
+    int64_t begin, end;          // the shard [begin, end)
+    int64_t now_ns;
+    int32_t mask_words;          // ceil((end − begin) / 64): the planes hold 64 · mask_words columns
+    int32_t commit;              // KG_CYCLE_COMMIT: reserve the winner
+    int32_t closed;              // the pod fails a node-independent gate (a required reservation, none loaded)
+    int32_t _pad;
+    unsigned long long *key;     // engine-owned device word: the launch's running best key (0 between launches)
+    uint32_t *ticket;            // engine-owned device word: workgroups arrived (0 between launches)
+    kg_cycle_out *out;           // engine-owned pinned host memory
+    unsigned long long *mask;    // PLANES outputs (device; any may be null)
+    uint16_t *scores;
+    uint8_t *numa;
+    unsigned long long *top1;
+};
+
+template <bool NUMA, bool PLANES>
+__global__ __launch_bounds__(256) void k_cycle_one(kg_consts c, kg_planes pl, kg_pod_dev p, CycleArgs a) {
+    __shared__ unsigned long long red[4];
+    __shared__ __attribute__((aligned(16))) typename std::conditional<NUMA, kg_pod_dev, int>::type lp;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (NUMA) {
+        if (tid == 0) lp = p;
+        __syncthreads();
+    }
+    const kg_pod_dev &pd = [&]() -> const kg_pod_dev & {
+        if constexpr (NUMA) return lp;
+        else return p;
+    }();
+    const int64_t col = (int64_t)blockIdx.x * 256 + tid;
+    const int64_t node = a.begin + col;
+    const bool in = node < a.end;
+    uint32_t fit = 0, la = 0, numa = 0;
+    bool feas = false;
+    if (in) {
+        NodeRegs n;
+        const BatchMasks bm{(c.plugins & KG_PLUGIN_FIT) ? pd.cmp_mask : 0u, (c.plugins & KG_PLUGIN_FIT) ? pd.fit_mask : 0u};
+        load_node(c, pl, node, true, bm, a.now_ns, n);
+        feas = eval_pair(c, pl, pd, n, node, a.now_ns, fit, la);
+        if constexpr (NUMA) {
+            if (PLANES || feas) {
+                const uint64_t ns = kg_numa_eval_any(c, pl.rows[node], pd);
+                feas = feas && (ns >> 32) != 0;
+                numa = (uint32_t)ns;
+            }
+        }
+        feas = feas && !a.closed;
+    }
+    if constexpr (PLANES) {
+        const unsigned long long word = __builtin_amdgcn_ballot_w64(feas);
+        [[maybe_unused]] const int64_t stride = (int64_t)a.mask_words * 64;   // (read by the bounds build alone)
+        // (a wave covers 64 columns from a multiple of 64: it writes its word when its first column is a node)
+        if (a.mask && lane == 0 && in && KG_IN(50, col >> 6, a.mask_words)) a.mask[col >> 6] = word;
+        if (a.scores && in && KG_IN(51, col, stride)) a.scores[col] = (uint16_t)(fit | (la << 8));
+        if (a.numa && in && KG_IN(52, col, stride)) a.numa[col] = (uint8_t)numa;
+    }
+    unsigned long long key = 0ull;
+    if (feas)
+        key = ((unsigned long long)(total_of(c, fit, la, numa) + 1u) << 32) | (0xFFFFFFFFull - (unsigned long long)node);
+    key = wave_max_u64(key);
+    if (lane == 0) red[wave] = key;
+    __syncthreads();
+    if (tid != 0) return;
+    unsigned long long best = red[0];
+#pragma unroll
+    for (int w = 1; w < 4; w++) best = red[w] > best ? red[w] : best;
+    kg_gu64 *gkey = (kg_gu64 *)a.key;
+    kg_gu32 *gticket = (kg_gu32 *)a.ticket;
+    if (best) (void)__hip_atomic_fetch_max(gkey, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the counter recipe: release, drain, then the ticket (in this order)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t t = __hip_atomic_fetch_add(gticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t != gridDim.x - 1) return;
+    // last arriver: every workgroup's max is in the word
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    best = __hip_atomic_exchange(gkey, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read and reset
+    __hip_atomic_store(gticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int32_t win = -1, committed = 0;
+    int64_t score = -1;
+    if (best) {
+        win = (int32_t)(0xFFFFFFFFull - (best & 0xFFFFFFFFull));
+        score = (int64_t)(best >> 32) - 1;
+        if (a.commit && win >= a.begin && KG_IN(53, win, a.end)) {   // k_commit_one's steps
+            if constexpr (NUMA) kg_numa_commit(c, pl.rows[win], pd);
+            kg_apply_commit(pl.rows[win], pd);
+            kg_finalize_node(c, pl, win);
+            committed = 1;
+        }
+    }
+    if (PLANES && a.top1) *a.top1 = best;
+    a.out->key = best;
+    a.out->node = win;
+    a.out->committed = committed;
+    a.out->score = score;
+}
+
+// ---------------------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------------------
 struct kg_engine {
@@ -3000,6 +3119,10 @@ struct kg_engine {
     kg_shm_comm *shm = nullptr;         // kg_comm_init_loopback: the host shared-memory communicator (kg_comm.cpp)
     uint32_t *shm_stage = nullptr;      // its pinned staging buffer (the slot size)
     uint32_t *comm_word = nullptr;      // device word of the status all-reduce (comm_agree)
+    // kg_cycle_one: the launch's key and ticket words (device, one 16-byte block, 0 between launches) and its
+    // result in pinned host memory; allocated at the first call
+    unsigned long long *cyc_words = nullptr;
+    kg_cycle_out *cyc_out = nullptr;
     int32_t comm_rank = 0, comm_world = 0;
     hipStream_t eval_stream = nullptr;  // kg_set_eval_stream (kg_place_chunk_eval), nullptr ⇒ stream
     // recorded on eval_stream after each kg_place_chunk_eval, one per partial buffer (keyed by its address): a chunk
@@ -3909,6 +4032,8 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->shm) kg_shm_comm_close(e->shm);
     if (e->shm_stage) (void)hipHostFree(e->shm_stage);
     if (e->comm_word) (void)hipFree(e->comm_word);
+    if (e->cyc_words) (void)hipFree(e->cyc_words);
+    if (e->cyc_out) (void)hipHostFree(e->cyc_out);
     if (e->hot_lax) (void)hipFree(e->hot_lax);
     if (e->eq_pods) (void)hipFree(e->eq_pods);
     if (e->eq_perm) (void)hipFree(e->eq_perm);
@@ -3999,6 +4124,8 @@ kg_status kg_snapshot_reset(kg_engine *e, int32_t n_nodes) {
     e->xslow_list = lax ? (int32_t *)carve(sizes[14]) : nullptr;
     e->xslow_count = lax ? (int32_t *)carve(sizes[15]) : nullptr;
     HIP_TRY(e, hipMemsetAsync(e->pl.rsv_of, 0xFF, sizes[11], e->stream));  // −1: no reservations
+    // kg_cycle_one's key and ticket: a launch that failed may have left them set (its last arriver resets them)
+    if (e->cyc_words) HIP_TRY(e, hipMemsetAsync(e->cyc_words, 0, 16, e->stream));
     if (e->rsv_mem) HIP_TRY(e, hipFree(e->rsv_mem));  // reservations refer to node indices: dropped
     e->rsv_mem = nullptr;
     e->rsv = nullptr;
@@ -5449,6 +5576,109 @@ kg_status kg_commit(kg_engine *e, int32_t pod, int32_t node) {
     if (failed) return set_err(e, KG_NOT_FOUND, "pod %d on node %d: not enough cpus available to satisfy request", pod, node);
     e->ctr.placed++;
     return KG_OK;
+}
+
+// One pod's scheduling cycle in one launch and one stream synchronisation (k_cycle_one); the uploaded batch
+// (pods, hot rows, class / eq tables) is not read and not replaced.
+kg_status kg_cycle_one(kg_engine *e, const kg_pod_row *pod, int64_t now_ns, uint32_t flags, const kg_eval_out *planes,
+                       kg_cycle_out *out) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (!pod || !out) return set_err(e, KG_ERR_INVALID_ARG, "null pod or output");
+    if (flags & ~KG_CYCLE_COMMIT) return set_err(e, KG_ERR_INVALID_ARG, "unknown kg_cycle_one flags 0x%x", flags);
+    if (planes && planes->rsv_scores) return set_err(e, KG_ERR_INVALID_ARG, "kg_cycle_one writes no rsv_scores plane");
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised");
+    const uint32_t plug = e->cfg.enabled_plugins;
+    const bool numa_on = (plug & KG_PLUGIN_NUMA) != 0;
+    if (!kg_pod_row_in_bounds(*pod)) return set_err(e, KG_ERR_RANGE, "pod: request outside the engine bounds");
+    const bool numa_pod = numa_on && !(pod->flags & KG_POD_NUMA_SKIP);
+    if (numa_pod && kg_numa_list_count(*pod) > KG_NUMA_MAX_LISTS)
+        return set_err(e, KG_ERR_UNSUPPORTED, "pod: more than %d NUMA hint lists", KG_NUMA_MAX_LISTS);
+    // what the fused launch does not answer keeps kg_pods_set + kg_eval + kg_commit
+    if ((plug & KG_PLUGIN_RESERVATION) && e->n_rn > 0)
+        return set_err(e, KG_ERR_UNSUPPORTED,
+                       "kg_cycle_one with reservation slots loaded (the preferred reservation and NormalizeScore reduce "
+                       "over every entry): use kg_pods_set + kg_eval + kg_commit");
+    if (plug & KG_PLUGIN_ELASTICQUOTA)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_cycle_one with ElasticQuota (the quota gate and its Reserve): use "
+                                              "kg_pods_set + kg_eval + kg_commit");
+    if ((numa_pod && (pod->flags & KG_POD_NUMA_CPU_BIND)) || (numa_on && e->n_node_bind_nodes > 0))
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_cycle_one does not bind cpusets (the Reserve takes the CPUs on the "
+                                              "host): use kg_pods_set + kg_eval + kg_commit");
+    if (!e->cyc_words) {
+        HIP_TRY(e, hipMalloc(&e->cyc_words, 16));
+        HIP_TRY(e, hipMemset(e->cyc_words, 0, 16));
+    }
+    if (!e->cyc_out) HIP_TRY(e, hipHostMalloc(&e->cyc_out, sizeof(kg_cycle_out), hipHostMallocDefault));
+    kg_pod_dev pd;
+    kg_pod_dev_from_row(e->cfg, *pod, pd);
+    const int64_t width = e->shard_end - e->shard_begin;
+    const int64_t words = (width + 63) / 64;
+    const bool dev = planes && planes->out_on_device != 0;
+    const bool want = planes && (planes->mask || planes->scores || planes->numa_scores);
+    const size_t mask_b = (size_t)words * 8, score_b = (size_t)width * 2, numa_b = (size_t)width;
+    e->ctr.eval_calls++;
+    e->ctr.evals += (uint64_t)width;
+    if (planes)
+        e->ctr.out_bytes += (planes->mask ? mask_b : 0) + (planes->scores ? score_b : 0) + (planes->top1 ? 8 : 0) +
+                            (planes->numa_scores ? numa_b : 0);
+    if (width <= 0) {   // an empty shard: nothing to launch
+        *out = kg_cycle_out{0, -1, 0, -1};
+        if (planes && planes->top1) {
+            if (dev) {
+                HIP_TRY(e, hipMemsetAsync(planes->top1, 0, 8, e->stream));
+                HIP_TRY(e, hipStreamSynchronize(e->stream));
+            } else {
+                planes->top1[0] = 0;
+            }
+        }
+        return KG_OK;
+    }
+    CycleArgs a{};
+    a.begin = e->shard_begin;
+    a.end = e->shard_end;
+    a.now_ns = now_ns;
+    a.mask_words = (int32_t)words;
+    a.commit = (flags & KG_CYCLE_COMMIT) ? 1 : 0;
+    a.closed = (pd.flags & KGP_RSV_REQUIRED) ? 1 : 0;   // a required reservation, and no slots are loaded
+    a.key = e->cyc_words;
+    a.ticket = (uint32_t *)(e->cyc_words + 1);
+    a.out = e->cyc_out;
+    if (want && dev) {
+        a.mask = (unsigned long long *)planes->mask;
+        a.scores = (uint16_t *)planes->scores;
+        a.numa = planes->numa_scores;
+    } else if (want) {   // host outputs: staged in scratch, copied back ahead of the one synchronisation
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        st = ensure_scratch(e, up(mask_b) + up((size_t)words * 128) + up((size_t)words * 64) + 256);
+        if (st) return st;
+        char *q = (char *)e->scratch;
+        if (planes->mask) a.mask = (unsigned long long *)q;
+        q += up(mask_b);
+        if (planes->scores) a.scores = (uint16_t *)q;
+        q += up((size_t)words * 128);
+        if (planes->numa_scores) a.numa = (uint8_t *)q;
+    }
+    if (dev && planes->top1) a.top1 = (unsigned long long *)planes->top1;
+    const bool with_planes = want || a.top1;
+    auto *kern = numa_on ? (with_planes ? k_cycle_one<true, true> : k_cycle_one<true, false>)
+                         : (with_planes ? k_cycle_one<false, true> : k_cycle_one<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((width + 255) / 256)), dim3(256), 0, e->stream, e->consts, e->pl, pd, a);
+    HIP_TRY(e, hipGetLastError());
+    if (want && !dev) {
+        if (planes->mask) HIP_TRY(e, hipMemcpyAsync(planes->mask, a.mask, mask_b, hipMemcpyDeviceToHost, e->stream));
+        if (planes->scores) HIP_TRY(e, hipMemcpyAsync(planes->scores, a.scores, score_b, hipMemcpyDeviceToHost, e->stream));
+        if (planes->numa_scores) HIP_TRY(e, hipMemcpyAsync(planes->numa_scores, a.numa, numa_b, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    *out = *e->cyc_out;
+    if (planes && planes->top1 && !dev) planes->top1[0] = out->key;
+    if (out->committed) {   // what host_reserve does after k_commit_one
+        e->slow_valid = false;
+        e->generation++;
+        e->ctr.placed++;
+    }
+    return bounds_verdict(e);
 }
 
 }  // extern "C"

@@ -330,6 +330,46 @@ class Engine:
         _check(st, self, "kg_commit")
         return True
 
+    def cycle_one(self, pod_row: np.ndarray, now_ns: int, commit: bool = True, planes: bool = False) -> dict:
+        """kg_cycle_one: the scheduling cycle of one pod (Filter + Score over the shard, selectHost and, with
+        `commit`, the Reserve of the chosen node) in one launch; the batch of set_pods is not touched.
+        Returns node (−1: none), score (−1: none), key (eval()'s top1 key) and committed; with `planes` also mask
+        [1][words] u64, scores [1][stride][2] u8 and numa_scores [1][stride] u8 of the snapshot before the commit.
+        Raises EngineError (KG_ERR_UNSUPPORTED) for what the fused launch does not answer — reservation slots,
+        ElasticQuota, cpuset binding: those callers keep set_pods + eval + commit."""
+        row = np.ascontiguousarray(pod_row, dtype=nat.POD_ROW).reshape(-1)
+        if len(row) != 1:
+            raise ValueError("cycle_one takes exactly one pod row")
+        res = {}
+        out = nat.CycleOut()
+        eo = None
+        if planes:
+            eo = nat.EvalOut()
+            res["mask"] = np.zeros((1, self.mask_words), dtype=np.uint64)
+            res["scores"] = np.zeros((1, self.score_stride, 2), dtype=np.uint8)
+            res["numa_scores"] = np.zeros((1, self.score_stride), dtype=np.uint8)
+            eo.mask, eo.scores, eo.numa_scores = (res[k].ctypes.data for k in ("mask", "scores", "numa_scores"))
+            eo.out_on_device = 0
+        _check(nat.lib().kg_cycle_one(self._h, nat.ptr(row), int(now_ns), nat.CYCLE_COMMIT if commit else 0,
+                                      ctypes.byref(eo) if eo is not None else None, ctypes.byref(out)), self,
+               "kg_cycle_one")
+        res.update(node=int(out.node), score=int(out.score), key=int(out.key), committed=bool(out.committed))
+        return res
+
+    def cycle_one_host(self, pod_row: np.ndarray, now_ns: int, commit: bool = True, mask_ptr: int = 0,
+                       scores_ptr: int = 0, numa_ptr: int = 0) -> "nat.CycleOut":
+        """kg_cycle_one with the planes in caller-owned host buffers (e.g. pinned memory, as eval_host): what the
+        Go plugins' per-pod loop calls (INTEGRATION.md `CycleOne`).  `pod_row`: a POD_ROW array of one row."""
+        out = nat.CycleOut()
+        eo = None
+        if mask_ptr or scores_ptr or numa_ptr:
+            eo = nat.EvalOut()
+            eo.mask, eo.scores, eo.numa_scores, eo.out_on_device = mask_ptr or None, scores_ptr or None, numa_ptr or None, 0
+        _check(nat.lib().kg_cycle_one(self._h, nat.ptr(pod_row), int(now_ns), nat.CYCLE_COMMIT if commit else 0,
+                                      ctypes.byref(eo) if eo is not None else None, ctypes.byref(out)), self,
+               "kg_cycle_one")
+        return out
+
     # Reservation / ElasticQuota -----------------------------------------------------------
     def set_reservations(self, rsv: np.ndarray) -> None:
         rsv = np.ascontiguousarray(rsv, dtype=nat.RESERVATION)
