@@ -531,8 +531,16 @@ typedef struct kg_engine kg_engine;
  *   numa_scores [P][64·W] uint8: NodeNUMAResource score (when KG_PLUGIN_NUMA is enabled)
  *   top1     [P] uint64: (total+1) << 32 | (0xFFFFFFFF − node) of the best feasible node,
  *            total = Σ weight·score, ties → lowest node index; 0 ⇔ no feasible node
+ * Pad columns [E − B, 64·W) of a row: the mask's pad bits (the high bits of its last word) are 0; the
+ * pad columns of scores, numa_scores and rsv_scores are unspecified (the kernels store whole vectors).
+ * Nothing outside the planes' [P][…] extents is written; a plane whose pointer is NULL is not touched.
+ * An empty range (B = E) writes top1 only.
  * When out_on_device != 0 the pointers are device pointers on the engine's device
- * (results stay resident; no copy back). */
+ * (results stay resident; no copy back).  Device outputs need no pre-zeroing: every in-range cell,
+ * every mask pad bit and every top1 key is written whatever the buffer held.  Each device pointer
+ * must be 16-byte aligned (the kernels store 16-byte vectors; rows of an odd W leave the mask's
+ * vector stores 8-byte aligned inside the plane, which the kernels allow for).
+ * (tests/test_matrix_guard_gpu.py holds all of this on guarded buffers.) */
 typedef struct kg_eval_out {
     uint64_t *mask;
     uint8_t *scores;

@@ -95,9 +95,11 @@ def _bounds_object() -> str:
 
 
 def build_bounds(force: bool = False, dev_obj: str | None = None) -> str:
-    """The bounds-checked engine (-DKG_BOUNDS_CHECK): every index into the pipelined placement's shared buffers is
-    checked on the device and a violation is reported by the next kg_place / kg_eval instead of faulting.  A debug
-    library beside the product one (loaded through KG_ENGINE_SO by tests/test_bounds_gpu.py, never by the product).
+    """The bounds-checked engine (-DKG_BOUNDS_CHECK): every index into the pipelined placement's shared buffers, into
+    kg_cycle_one's planes and into the matrix-mode outputs is checked on the device and a violation is reported by the
+    kg_place / kg_cycle_one / kg_eval call that ran the kernel instead of faulting.  A debug library beside the product
+    one (loaded through KG_ENGINE_SO by tests/test_bounds_gpu.py, test_cycle_one_bounds_gpu.py and
+    test_matrix_bounds_gpu.py, never by the product).
     `dev_obj`: its device object, already compiled (build_all compiles it beside the product's)."""
     if dev_obj is None:
         if not force and not _newer(BOUNDS_SO, engine_sources()):

@@ -51,9 +51,33 @@
 
 // Bounds-checked build (-DKG_BOUNDS_CHECK, koordinator_amd/build.py build_bounds → lib/libkoordgpu_bounds.so): the
 // indices of the pipelined placement's shared buffers (previous-chunk lists, pvkeys, the outcome cache, the touched
-// lists, the partial keys) are checked before use; a violation is recorded (count, first site / index / bound) and
-// the access skipped, and the next kg_place / kg_eval returns KG_ERR_STATE naming it — a test reads the violation
-// instead of faulting the GPU.  The product build compiles every check to `true`.
+// lists, the partial keys), of kg_cycle_one's planes and of every matrix-mode output (mask, score pairs, NUMA and
+// Reservation planes, per-(pod, tile) keys, top1) are checked before use; a violation is recorded (count, first
+// site / index / bound) and the access skipped, and the kg_place / kg_place_sharded / kg_cycle_one / kg_eval call
+// that ran the kernel returns KG_ERR_STATE naming it — a test reads the violation instead of faulting the GPU.
+// The product build compiles every check to `true`.  A matrix site checks the output row against the launch's row
+// count and the column (of a vector access: its last element) against the row's width, so a store that leaves its
+// own row is caught even where it stays inside the buffer.
+//   site  kernel                      buffer
+//   10-11 k_prev_keys                 previous-chunk list, pod
+//   20    k_ncache_refresh            outcome cache
+//   30-31 k_eval_numa_cached          class of the pod, outcome cache column
+//   40-46 k_resolve                   touched list, prevq, rescan list, touched count, winner, slow list, node
+//   50-53 k_cycle_one                 mask, score pairs, NUMA plane, committed node
+//   60-62 k_eval2 (hot_loop2)         score pairs, mask words, tile keys
+//   63-65 k_eval3 (cls_block)         score pairs, mask words, tile keys
+//   66-68 k_eval3_dup (cls_block_dup) score pairs, mask words, tile keys
+//   69-71 k_eval3 / k_eval3_dup       class work table, class descriptors, pod ids / row indices (reads)
+//   72-74 k_fix_slow                  score pairs, mask words, tile keys
+//   75-77 k_eval_exact                score pairs, mask words, tile keys
+//   78-81 k_numa_bind_fix             score pairs, NUMA plane, mask words, tile keys
+//   82-83 k_eval_numa2 (numa2_run)    COMBINE read-backs: score pairs, mask half-words
+//   84-88 k_eval_numa2 (numa2_run)    score flush, NUMA flush, mask word, tail mask half-word, tile keys
+//   89-90 k_top1                      tile keys (read), top1
+//   91-93 k_rsv_eval                  score pairs, NUMA plane, mask words
+//   94-95 k_rsv_reduce                top1, Reservation plane (rsv_best_block)
+//   96-98 k_quota_apply               mask words, Reservation plane, top1
+//   99-100 k_eq_rows                  distinct row (read), output row vector
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -69,6 +93,8 @@ __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
 #else
 #define KG_IN(site, idx, bound) true
 #endif
+// row `row` of `rows`, column `col` of a `cols`-wide row
+#define KG_IN2(site, row, rows, col, cols) (KG_IN(site, row, rows) && KG_IN(site, col, cols))
 
 // ---------------------------------------------------------------------------------------
 // wave reductions
@@ -340,6 +366,9 @@ struct HotArgs {
     int32_t lax_x[KG_LAX];
     uint32_t lax_w[KG_LAX];
     const double *lax_est;
+#ifdef KG_BOUNDS_CHECK
+    int32_t cls_ndesc, cls_nwork, cls_nids;   // entries of the class descriptors, this launch's work items, the ids
+#endif
 };
 
 // ---------------------------------------------------------------------------------------
@@ -497,10 +526,14 @@ __device__ __forceinline__ void hot_loop2(const kg_consts &c, const HotArgs &a, 
         const bool ok1 = eval_hot<S, FAST, LA_PROD, FULL, LAX>(c, a, pd, n1, fit1, la1, lx);
         if (OUT) {
             uint16_t *s = srow + (int64_t)p * a.score_stride;
-            if (seg0) s[0] = (uint16_t)(fit0 | (la0 << 8));
-            if (seg1) s[64] = (uint16_t)(fit1 | (la1 << 8));
+            // (bounds build: the wave's first column, as k_eval2 derives it)
+#define KG_EVAL2_COL0 (((int64_t)(a.tile_begin + blockIdx.x) * KG_TILE + (threadIdx.x >> 6) * 128) - a.col_begin)
+            if (seg0 && KG_IN2(60, p, a.n_pods, KG_EVAL2_COL0 + lane, a.score_stride)) s[0] = (uint16_t)(fit0 | (la0 << 8));
+            if (seg1 && KG_IN2(60, p, a.n_pods, KG_EVAL2_COL0 + 64 + lane, a.score_stride)) s[64] = (uint16_t)(fit1 | (la1 << 8));
             const unsigned long long b0 = __ballot(ok0), b1 = __ballot(ok1);
-            if (lane < mask_lanes) mrow[(int64_t)p * a.mask_words + lane] = lane ? b1 : b0;
+            if (lane < mask_lanes && KG_IN2(61, p, a.n_pods, (KG_EVAL2_COL0 >> 6) + lane, a.mask_words))
+                mrow[(int64_t)p * a.mask_words + lane] = lane ? b1 : b0;
+#undef KG_EVAL2_COL0
         }
         uint32_t tot0, tot1;
         if (FAST) {
@@ -616,7 +649,8 @@ __global__ __launch_bounds__(KG_BLOCK) void k_eval2(kg_consts c, kg_planes pl, H
         mx = dpp_max_step(mx, 2);
         mx = dpp_max_step(mx, 3);
         mx = dpp_max_step(mx, 4);
-        if (rg == 31 && rj < p1 - p0) partials[(int64_t)(p0 + rj) * a.tiles_total + tile] = mx;
+        if (rg == 31 && rj < p1 - p0 && KG_IN2(62, p0 + rj, a.n_pods, tile, a.tiles_total))
+            partials[(int64_t)(p0 + rj) * a.tiles_total + tile] = mx;
         __syncthreads();
     }
 }
@@ -945,7 +979,7 @@ __device__ __forceinline__ void cls_block(const kg_consts &c, const kg_planes &p
     // the work item's output rows (for the stores and the partial keys) go to LDS once: the chunk loop issues no
     // vector loads, so nothing in it waits on vmcnt — i.e. on its own score stores
     const kg_pod_cls_t<NC, NF> *grows = reinterpret_cast<const kg_pod_cls_t<NC, NF> *>(rows_base + d.rows_offset);
-    if (tid < w.end - w.begin) lid[tid] = ids[d.ids_first + w.begin + tid];
+    if (tid < w.end - w.begin) lid[tid] = KG_IN(71, d.ids_first + w.begin + tid, a.cls_nids) ? ids[d.ids_first + w.begin + tid] : -1;
     // every node-plane load has landed before the pod loop: the loop itself then never waits on
     // vector memory (its stores included)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
@@ -996,14 +1030,14 @@ __device__ __forceinline__ void cls_block(const kg_consts &c, const kg_planes &p
 #pragma unroll
             for (int it = 0; it < CC / PPS; it++) {
                 const int pp = it * PPS + lane / LP;
-                if (whole || (pp < np && segs)) {
+                if ((whole || (pp < np && segs)) && KG_IN2(63, cur[pp], a.n_pods, col0 + s8 * 8 + 7, a.score_stride)) {
                     const uint4 v = *reinterpret_cast<const uint4 *>(sst + pp * SEGW + s8 * 8);
                     const int64_t off = (int64_t)cur[pp] * a.score_stride;
                     // non-temporal (a write-once stream): plain stores of the same data measured 0.94 vs 0.67 ms per pass
                     __builtin_nontemporal_store(u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4 *>(scores + off + col0 + s8 * 8));
                 }
             }
-            if (lane < np && seg[0]) {
+            if (lane < np && seg[0] && KG_IN2(64, cur[lane], a.n_pods, (col0 >> 6) + (seg[1] ? 1 : 0), a.mask_words)) {
                 // lane l writes the two feasibility words of pod p0 + l
                 uint64_t *mw = mask + (int64_t)cur[lane] * a.mask_words + (col0 >> 6);
                 mw[0] = mb[0];
@@ -1028,7 +1062,7 @@ __device__ __forceinline__ void cls_block(const kg_consts &c, const kg_planes &p
             mx = max(mx, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0x141, 0xf, 0xf, false));  // row_half_mirror
             mx = max(mx, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0x4e, 0xf, 0xf, false));   // quad_perm 2,3,0,1
             mx = max(mx, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0xb1, 0xf, 0xf, false));   // quad_perm 1,0,3,2
-            if (q == 0 && p < p1 - p0) {
+            if (q == 0 && p < p1 - p0 && KG_IN2(65, cur[p], a.n_pods, tile, a.tiles_total)) {
                 partials[(int64_t)cur[p] * a.tiles_total + tile] = mx;
             }
         }
@@ -1083,10 +1117,11 @@ __device__ __forceinline__ void cls_block_dup(const kg_consts &c, const kg_plane
     // the item's pods (output rows) and their row indices relative to the item's first row go to LDS
     const int nm = w.end - w.begin;
     const int32_t *uxs = ids + d.ux_first + w.begin;
-    const int32_t u_first = uxs[0];
+    const int32_t u_first = KG_IN(71, d.ux_first + w.begin, a.cls_nids) ? uxs[0] : 0;
     if (tid < nm) {
-        lid[tid] = ids[d.ids_first + w.begin + tid];
-        lux[tid] = (uint16_t)(uxs[tid] - u_first);
+        const bool in = KG_IN(71, d.ids_first + w.begin + tid, a.cls_nids) && KG_IN(71, d.ux_first + w.begin + tid, a.cls_nids);
+        lid[tid] = in ? ids[d.ids_first + w.begin + tid] : -1;
+        lux[tid] = in ? (uint16_t)(uxs[tid] - u_first) : (uint16_t)0;
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the pod loops then never wait on vector memory
     __syncthreads();
@@ -1123,7 +1158,7 @@ __device__ __forceinline__ void cls_block_dup(const kg_consts &c, const kg_plane
             // 16 lanes × 16 B = one pod's 128 columns: 4 pods per wave store
             for (int m = m0; m < m1; m += 4) {
                 const int mm = m + (lane >> 4);
-                if (mm < m1 && segs) {
+                if (mm < m1 && segs && KG_IN2(66, lid[mm], a.n_pods, col0 + s8 * 8 + 7, a.score_stride)) {
                     const int u = lux[mm] - u0;
                     const uint4 v = *reinterpret_cast<const uint4 *>(sst + u * SEGW + s8 * 8);
                     const int64_t off = (int64_t)lid[mm] * a.score_stride;
@@ -1146,7 +1181,8 @@ __device__ __forceinline__ void cls_block_dup(const kg_consts &c, const kg_plane
             const int64_t c0 = (wave_base - wave * SEGW - a.col_begin) + wl * SEGW;   // tile column of segment wl
             for (int m = m0 + wave * 8; m < m1; m += 64) {
                 const int mm = m + sub;
-                if (mm < m1 && c0 < a.score_stride) {
+                if (mm < m1 && c0 < a.score_stride &&
+                    KG_IN2(67, lid[mm], a.n_pods, (c0 >> 6) + (c0 + 64 < a.score_stride ? 1 : 0), a.mask_words)) {
                     const uint4 v = mstage[((ci & 1) * CC + (lux[mm] - u0)) * 8 + wl];
                     uint64_t *mw = mask + (int64_t)lid[mm] * a.mask_words + (c0 >> 6);
                     if (c0 + 64 < a.score_stride) {
@@ -1174,7 +1210,7 @@ __device__ __forceinline__ void cls_block_dup(const kg_consts &c, const kg_plane
                 const int mm = m + lane;
                 const int u = mm < m1 ? lux[mm] - u0 : 0;
                 const uint32_t k = (uint32_t)__builtin_amdgcn_ds_bpermute(u << 5, (int)mx);
-                if (mm < m1) partials[(int64_t)lid[mm] * a.tiles_total + tile] = k;
+                if (mm < m1 && KG_IN2(68, lid[mm], a.n_pods, tile, a.tiles_total)) partials[(int64_t)lid[mm] * a.tiles_total + tile] = k;
             }
         }
     }
@@ -1201,7 +1237,9 @@ __global__ __launch_bounds__(KG_TILE / 2) __attribute__((amdgpu_waves_per_eu(KIN
     const int per = (int)(gridDim.x / KG_XCDS);
     const int item = (int)(blockIdx.x % KG_XCDS) * per + (int)(blockIdx.x / KG_XCDS);
     if (item >= n_items) return;   // grid padded to a multiple of 8; block-uniform
+    if (!KG_IN(69, item, a.cls_nwork)) return;
     const kg_cls_work w = work[item];
+    if (!KG_IN(70, w.cls, a.cls_ndesc)) return;   // (block-uniform)
     const kg_cls_desc d = descs[w.cls];
 #define KG_CLS_ARGS c, pl, a, d, w, rows, ids, mask, scores, partials, kbuf, lid, lux, cst, sstage, mstage
     if constexpr (KIND == 0) cls_block_dup<2, 2, MOST, FIT_ON, LA_ON, OUT, W1>(KG_CLS_ARGS);
@@ -1225,7 +1263,9 @@ __global__ __launch_bounds__(KG_TILE / 2) __attribute__((amdgpu_waves_per_eu(KIN
     static_assert(CC * BT <= 4096, "a chunk's keys fit the key buffer");
     __shared__ int32_t lid[KG_CLS_ITEM_MAX];
     __shared__ __attribute__((aligned(16))) uint16_t sstage[OUT ? (BT / 64) * CC * 128 : 8];
+    if (!KG_IN(69, blockIdx.y, a.cls_nwork)) return;
     const kg_cls_work w = work[blockIdx.y];
+    if (!KG_IN(70, w.cls, a.cls_ndesc)) return;   // (block-uniform)
     const kg_cls_desc d = descs[w.cls];
 #define KG_CLS_ARGS c, pl, a, d, w, rows, ids, mask, scores, partials, kbuf, lid, sstage
     if constexpr (KIND == 0) cls_block<2, 2, MOST, FIT_ON, LA_ON, OUT, W1, LAU>(KG_CLS_ARGS);
@@ -1237,16 +1277,22 @@ __global__ __launch_bounds__(KG_TILE / 2) __attribute__((amdgpu_waves_per_eu(KIN
 
 // Pod equivalence (kg_engine::eq_on): row p of an output plane := row of[p] of the distinct batch's plane.  VB-byte
 // vectors, non-temporal stores (a write-once stream); the distinct rows stay in L2 / MALL across their pods.
+#ifdef KG_BOUNDS_CHECK   // (the bounds build also passes the number of distinct rows)
+#define KG_EQ_NSRC(n) , n
+#else
+#define KG_EQ_NSRC(n)
+#endif
 template <int VB>
 __global__ __launch_bounds__(256) void k_eq_rows(const int32_t *__restrict__ of, int32_t P, const char *__restrict__ src,
-                                                 char *__restrict__ dst, int64_t row_bytes) {
+                                                 char *__restrict__ dst, int64_t row_bytes KG_EQ_NSRC(int32_t n_src)) {
     typedef uint32_t vec_t __attribute__((ext_vector_type(VB / 4)));
     const int64_t nv = row_bytes / VB;
     for (int32_t p = blockIdx.y; p < P; p += gridDim.y) {
+        if (!KG_IN(99, of[p], n_src)) continue;
         const vec_t *s = reinterpret_cast<const vec_t *>(src + (int64_t)of[p] * row_bytes);
         vec_t *d = reinterpret_cast<vec_t *>(dst + (int64_t)p * row_bytes);
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x)
-            __builtin_nontemporal_store(s[i], d + i);
+            if (KG_IN(100, (i + 1) * VB - 1, row_bytes)) __builtin_nontemporal_store(s[i], d + i);
     }
 }
 
@@ -1273,12 +1319,13 @@ __global__ void k_fix_slow(kg_consts c, kg_planes pl, const kg_pod_dev *__restri
         uint32_t fit, la;
         kg_pair_exact(c, pl.rows[node], pl.dflags[node], pods[p], now_ns, feas, fit, la);
         const int64_t col = node - col_begin;
-        if (scores) scores[(int64_t)p * score_stride + col] = (uint16_t)(fit | (la << 8));
+        if (scores && KG_IN2(72, p, n_pods, col, score_stride)) scores[(int64_t)p * score_stride + col] = (uint16_t)(fit | (la << 8));
         if (feas) {
-            if (mask) atomicOr(&mask[(int64_t)p * mask_words + (col >> 6)], 1ull << (col & 63));
+            if (mask && KG_IN2(73, p, n_pods, col >> 6, mask_words))
+                atomicOr(&mask[(int64_t)p * mask_words + (col >> 6)], 1ull << (col & 63));
             const uint32_t tot = (uint32_t)c.weight_fit * fit + (uint32_t)c.weight_la * la;
             const uint32_t key = ((tot + 1u) << KG_TILE_SHIFT) | (uint32_t)(KG_TILE - 1 - (node % KG_TILE));
-            atomicMax(&partials[(int64_t)p * tiles_total + node / KG_TILE], key);
+            if (KG_IN2(74, p, n_pods, node / KG_TILE, tiles_total)) atomicMax(&partials[(int64_t)p * tiles_total + node / KG_TILE], key);
         }
     }
 }
@@ -1299,16 +1346,18 @@ __global__ __launch_bounds__(256) void k_eval_exact(kg_consts c, kg_planes pl, c
         bool feas = false;
         uint32_t fit = 0, la = 0;
         if (own) kg_pair_exact(c, pl.rows[node], df, pods[p], now_ns, feas, fit, la);
-        if (own && scores) scores[(int64_t)p * score_stride + col] = (uint16_t)(fit | (la << 8));
+        if (own && scores && KG_IN2(75, p, n_pods, col, score_stride)) scores[(int64_t)p * score_stride + col] = (uint16_t)(fit | (la << 8));
         const unsigned long long word = __builtin_amdgcn_ballot_w64(feas);
-        if (mask && (threadIdx.x & 63) == 0 && (col >> 6) < mask_words && in) mask[(int64_t)p * mask_words + (col >> 6)] = word;
+        if (mask && (threadIdx.x & 63) == 0 && (col >> 6) < mask_words && in && KG_IN2(76, p, n_pods, col >> 6, mask_words))
+            mask[(int64_t)p * mask_words + (col >> 6)] = word;
         uint32_t key = 0;
         if (feas) {
             const uint32_t tot = (uint32_t)c.weight_fit * fit + (uint32_t)c.weight_la * la;
             key = ((tot + 1u) << KG_TILE_SHIFT) | (uint32_t)(KG_TILE - 1 - (node % KG_TILE));
         }
         key = wave_max_u32(key);
-        if ((threadIdx.x & 63) == 0 && key) atomicMax(&partials[(int64_t)p * tiles_total + node / KG_TILE], key);
+        if ((threadIdx.x & 63) == 0 && key && KG_IN2(77, p, n_pods, node / KG_TILE, tiles_total))
+            atomicMax(&partials[(int64_t)p * tiles_total + node / KG_TILE], key);
     }
 }
 
@@ -1340,12 +1389,13 @@ __global__ __launch_bounds__(256) void k_numa_bind_fix(kg_consts c, kg_planes pl
         kg_numa_out o;
         kg_numa_pair_z<kg_zone_calc, true>(c, row, pd, o, kg_zone_calc{row});
         ok = ok && o.feasible;
-        if (scores) scores[(int64_t)p * a.score_stride + col] = (uint16_t)(fit | (la << 8));
-        if (numa_scores) numa_scores[(int64_t)p * a.score_stride + col] = (uint8_t)o.score;
+        if (scores && KG_IN2(78, p, a.n_pods, col, a.score_stride)) scores[(int64_t)p * a.score_stride + col] = (uint16_t)(fit | (la << 8));
+        if (numa_scores && KG_IN2(79, p, a.n_pods, col, a.score_stride)) numa_scores[(int64_t)p * a.score_stride + col] = (uint8_t)o.score;
         if (ok) {
-            if (mask) atomicOr(&mask[(int64_t)p * a.mask_words + (col >> 6)], 1ull << (col & 63));
+            if (mask && KG_IN2(80, p, a.n_pods, col >> 6, a.mask_words))
+                atomicOr(&mask[(int64_t)p * a.mask_words + (col >> 6)], 1ull << (col & 63));
             const uint32_t key = ((total_of(c, fit, la, o.score) + 1u) << KG_TILE_SHIFT) | (uint32_t)(KG_TILE - 1 - (node % KG_TILE));
-            atomicMax(&partials[(int64_t)p * a.tiles_total + node / KG_TILE], key);
+            if (KG_IN2(81, p, a.n_pods, node / KG_TILE, a.tiles_total)) atomicMax(&partials[(int64_t)p * a.tiles_total + node / KG_TILE], key);
         }
     }
 }
@@ -1422,7 +1472,7 @@ __device__ __forceinline__ void numa2_run(const kg_consts &c, const kg_planes &p
         bool ok = false;
         if (COMBINE && (k & (FL - 1)) == 0) {   // (runs start on a 32-node boundary: k = 0 begins a segment)
             const int64_t c0 = node - a.col_begin;
-            const bool have = live && in_range && c0 < a.score_stride;
+            const bool have = live && in_range && c0 < a.score_stride && KG_IN2(82, p, a.n_pods, c0 + FL - 1, a.score_stride);
             const kg_u32x4 *src = reinterpret_cast<const kg_u32x4 *>(scores + (int64_t)p * a.score_stride + c0);
 #pragma unroll
             for (int i = 0; i < FL / 8; i++) {
@@ -1435,7 +1485,7 @@ __device__ __forceinline__ void numa2_run(const kg_consts &c, const kg_planes &p
         }
         if (COMBINE && (k & 31) == 0) {
             const int64_t c0 = node - a.col_begin;
-            min32 = live && in_range && c0 < (int64_t)a.mask_words * 64
+            min32 = live && in_range && c0 < (int64_t)a.mask_words * 64 && KG_IN2(83, p, a.n_pods, c0 >> 5, 2 * (int64_t)a.mask_words)
                         ? reinterpret_cast<const uint32_t *>(mask + (int64_t)p * a.mask_words)[c0 >> 5] : 0u;
         }
         if (in_range) {  // wave-uniform branch
@@ -1550,13 +1600,13 @@ __device__ __forceinline__ void numa2_run(const kg_consts &c, const kg_planes &p
         const int64_t col = node - a.col_begin;
         if ((k & (FL - 1)) == FL - 1) {
             const int64_t c0 = col - (FL - 1);
-            if (!COMBINE && live && scores && c0 < a.score_stride) {
+            if (!COMBINE && live && scores && c0 < a.score_stride && KG_IN2(84, p, a.n_pods, c0 + FL - 1, a.score_stride)) {
                 kg_u32x4 *d = reinterpret_cast<kg_u32x4 *>(scores + (int64_t)p * a.score_stride + c0);
 #pragma unroll
                 for (int i = 0; i < FL / 8; i++)
                     __builtin_nontemporal_store(kg_u32x4{sacc[4 * i], sacc[4 * i + 1], sacc[4 * i + 2], sacc[4 * i + 3]}, d + i);
             }
-            if (live && numa_scores && c0 < a.score_stride) {
+            if (live && numa_scores && c0 < a.score_stride && KG_IN2(85, p, a.n_pods, c0 + FL - 1, a.score_stride)) {
                 kg_u32x4 *d = reinterpret_cast<kg_u32x4 *>(numa_scores + (int64_t)p * a.score_stride + c0);
 #pragma unroll
                 for (int i = 0; i < FL / 16; i++)
@@ -1569,16 +1619,17 @@ __device__ __forceinline__ void numa2_run(const kg_consts &c, const kg_planes &p
         }
         if ((k & 63) == 63) {
             const int64_t c0 = col - 63;
-            if (live && mask && c0 < (int64_t)a.mask_words * 64) mask[(int64_t)p * a.mask_words + (c0 >> 6)] = mword;
+            if (live && mask && c0 < (int64_t)a.mask_words * 64 && KG_IN2(86, p, a.n_pods, c0 >> 6, a.mask_words))
+                mask[(int64_t)p * a.mask_words + (c0 >> 6)] = mword;
             mword = 0;
         }
     }
     if (npw & 63) {  // a 32-node run: its half of the mask word (little-endian: low half = first 32 nodes)
         const int64_t c0 = base + npw - 32 - a.col_begin;
-        if (live && mask && c0 < (int64_t)a.mask_words * 64)
+        if (live && mask && c0 < (int64_t)a.mask_words * 64 && KG_IN2(87, p, a.n_pods, c0 >> 5, 2 * (int64_t)a.mask_words))
             reinterpret_cast<uint32_t *>(mask + (int64_t)p * a.mask_words)[c0 >> 5] = (uint32_t)mword;
     }
-    if (live && best) atomicMax(&partials[(int64_t)p * a.tiles_total + tile], best);
+    if (live && best && KG_IN2(88, p, a.n_pods, tile, a.tiles_total)) atomicMax(&partials[(int64_t)p * a.tiles_total + tile], best);
 }
 
 // NodeNUMAResource enabled (config 3; matrix mode and placement chunks), pod per lane: a wave holds 64 pods and
@@ -1654,11 +1705,11 @@ __global__ void k_top1(const uint32_t *__restrict__ partials, int32_t tiles, int
     if (wave >= n_pods) return;
     unsigned long long best = 0;
     for (int t = lane; t < tiles; t += 64) {
-        unsigned long long k = decode_partial(partials[(int64_t)wave * tiles + t], t);
+        unsigned long long k = KG_IN2(89, wave, n_pods, t, tiles) ? decode_partial(partials[(int64_t)wave * tiles + t], t) : 0ull;
         best = best > k ? best : k;
     }
     best = wave_max_u64(best);
-    if (lane == 0) out[wave] = best;
+    if (lane == 0 && KG_IN(90, wave, n_pods)) out[wave] = best;
 }
 
 // NUMA: the resolve instantiation may meet NodeNUMAResource (the plain one carries no NUMA code)
@@ -1976,7 +2027,8 @@ __device__ unsigned long long rsv_best_block(const kg_consts &c, const unsigned 
                 const unsigned long long key = ((total + 1ull) << 32) | (0xFFFFFFFFull - (unsigned long long)node);
                 best = best > key ? best : key;
             }
-            if (plane && node >= col_begin && node < col_end) plane[node - col_begin] = (uint8_t)sn;
+            if (plane && node >= col_begin && node < col_end && KG_IN(95, node - col_begin, col_end - col_begin))
+                plane[node - col_begin] = (uint8_t)sn;
         }
     }
     best = wave_max_u64(best);
@@ -2178,9 +2230,9 @@ __global__ __launch_bounds__(256) void k_rsv_eval(kg_consts c, kg_planes pl, Rsv
     const int64_t node = nd;
     if (scores && node >= col_begin && node < col_end) {
         const int64_t col = node - col_begin;
-        scores[(int64_t)p * score_stride + col] = (uint16_t)(r.fit | (r.la << 8));
-        if (numa_scores) numa_scores[(int64_t)p * score_stride + col] = (uint8_t)r.numa;
-        if (r.feasible) atomicOr(&mask[(int64_t)p * mask_words + (col >> 6)], 1ull << (col & 63));
+        if (KG_IN2(91, p, P, col, score_stride)) scores[(int64_t)p * score_stride + col] = (uint16_t)(r.fit | (r.la << 8));
+        if (numa_scores && KG_IN2(92, p, P, col, score_stride)) numa_scores[(int64_t)p * score_stride + col] = (uint8_t)r.numa;
+        if (r.feasible && KG_IN2(93, p, P, col >> 6, mask_words)) atomicOr(&mask[(int64_t)p * mask_words + (col >> 6)], 1ull << (col & 63));
     }
 }
 
@@ -2195,7 +2247,7 @@ __global__ __launch_bounds__(256) void k_rsv_reduce(kg_consts c, RsvArgs ra, int
     const unsigned long long best = rsv_best_block<256>(c, ra.E + (int64_t)p * ra.n_rn, ra.O + (int64_t)p * ra.n_rn,
                                                         ra.rnode, ra.n_rn, plane ? plane + (int64_t)p * plane_stride : nullptr,
                                                         col_begin, col_end, red, redo);
-    if (threadIdx.x == 0 && top1 && best > top1[p]) top1[p] = best;
+    if (threadIdx.x == 0 && top1 && KG_IN(94, p, P) && best > top1[p]) top1[p] = best;
 }
 
 // ElasticQuota PreFilter of pods [0, P) against the current quota state
@@ -2215,10 +2267,12 @@ __global__ void k_quota_apply(const uint8_t *__restrict__ gate, int32_t P, unsig
     const int32_t p = blockIdx.x;
     if (p >= P || gate[p]) return;
     if (mask)
-        for (int32_t w = threadIdx.x; w < mask_words; w += blockDim.x) mask[(int64_t)p * mask_words + w] = 0ull;
+        for (int32_t w = threadIdx.x; w < mask_words; w += blockDim.x)
+            if (KG_IN2(96, p, P, w, mask_words)) mask[(int64_t)p * mask_words + w] = 0ull;
     if (plane)
-        for (int64_t w = threadIdx.x; w < plane_stride; w += blockDim.x) plane[p * plane_stride + w] = 0;
-    if (top1 && threadIdx.x == 0) top1[p] = 0ull;
+        for (int64_t w = threadIdx.x; w < plane_stride; w += blockDim.x)
+            if (KG_IN2(97, p, P, w, plane_stride)) plane[p * plane_stride + w] = 0;
+    if (top1 && threadIdx.x == 0 && KG_IN(98, p, P)) top1[p] = 0ull;
 }
 
 // Reserve of the Reservation (nominated slot) and ElasticQuota (used) parts on `node`.
@@ -3055,6 +3109,7 @@ struct kg_engine {
     void *cls_mem = nullptr;                // device: descs | work | rows
     size_t cls_mem_bytes = 0;
     int32_t cls_nwork = 0;
+    int32_t cls_nids = 0;                   // entries of the class id table (the bounds build checks its reads)
     int32_t cls_kind_work[12][2] = {};  // [3 · kind + form] = (first work item, count); form 0 mixed, 1 LoadAware-
                                         // uniform, 2 duplicate-row (its items carry their tile)
     size_t cls_work_off = 0, cls_rows_off = 0, cls_ids_off = 0;
@@ -3589,6 +3644,7 @@ kg_status cls_layout(kg_engine *e, int64_t width, int64_t shard_tiles) {
     HIP_TRY(e, h2d(e, m + e->cls_ids_off, ids.data(), ids.size() * 4, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));   // the host vectors end with this call
     e->cls_nwork = (int32_t)work.size();
+    e->cls_nids = n_ids;
     e->cls_width = width;
     e->cls_tiles = shard_tiles;
     e->cls_dirty = false;
@@ -3596,12 +3652,20 @@ kg_status cls_layout(kg_engine *e, int64_t width, int64_t shard_tiles) {
 }
 
 template <bool MOST, bool FIT_ON, bool LA_ON, bool W1, int KIND, int FORM>
-void launch_cls_kind(kg_engine *e, dim3 grid, const HotArgs &a, const kg_cls_desc *descs, const kg_cls_work *work,
+void launch_cls_kind(kg_engine *e, dim3 grid, const HotArgs &a_in, const kg_cls_desc *descs, const kg_cls_work *work,
                      const char *rows, const int32_t *ids, uint64_t *mask, uint16_t *scores, uint32_t *partials,
                      hipStream_t stream) {
     constexpr bool LAU = FORM == 1;
     const int32_t first = e->cls_kind_work[3 * KIND + FORM][0], count = e->cls_kind_work[3 * KIND + FORM][1];
     if (count == 0) return;
+#ifdef KG_BOUNDS_CHECK
+    HotArgs a = a_in;
+    a.cls_ndesc = (int32_t)e->cls_desc.size();
+    a.cls_nwork = count;
+    a.cls_nids = e->cls_nids;
+#else
+    const HotArgs &a = a_in;
+#endif
     if constexpr (LAU && !LA_ON) return;   // (no such work items: cls_order_la)
     else if constexpr (FORM == 2) {
         const dim3 g1((unsigned)((count + KG_XCDS - 1) / KG_XCDS * KG_XCDS));
@@ -4553,7 +4617,7 @@ kg_status kg_eval(kg_engine *e, int64_t now_ns, const kg_eval_out *out) {
         if (out->rsv_scores && P > 0) HIP_TRY(e, hipMemcpyAsync(out->rsv_scores, rsvp, numa_b, hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(e, hipStreamSynchronize(e->stream));
     }
-    return KG_OK;
+    return bounds_verdict(e);
 }
 
 }  // extern "C"
@@ -4622,10 +4686,10 @@ kg_status eval_eq(kg_engine *e, int64_t now_ns, const kg_eval_out *out) {
         const dim3 grid(gx > 0 ? gx : 1, (unsigned)std::min<int32_t>(P, 65535));
         if (rb[k] % 16 == 0)
             hipLaunchKernelGGL(k_eq_rows<16>, grid, dim3(256), 0, e->stream, e->eq_of, P, (const char *)(m + off_c[k]), dst,
-                               (int64_t)rb[k]);
+                               (int64_t)rb[k] KG_EQ_NSRC(U));
         else
             hipLaunchKernelGGL(k_eq_rows<8>, grid, dim3(256), 0, e->stream, e->eq_of, P, (const char *)(m + off_c[k]), dst,
-                               (int64_t)rb[k]);
+                               (int64_t)rb[k] KG_EQ_NSRC(U));
         HIP_TRY(e, hipGetLastError());
     }
     if (!dev) {
@@ -4633,7 +4697,7 @@ kg_status eval_eq(kg_engine *e, int64_t now_ns, const kg_eval_out *out) {
             if (want[k]) HIP_TRY(e, hipMemcpyAsync(want[k], m + off_s[k], rb[k] * (size_t)P, hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(e, hipStreamSynchronize(e->stream));
     }
-    return KG_OK;
+    return bounds_verdict(e);
 }
 
 kg_status chunk_eval(kg_engine *e, int64_t now_ns, int32_t pod_begin, int32_t n, uint32_t *partial_dev) {

@@ -233,10 +233,12 @@ class Engine:
         return res
 
     def eval_device(self, now_ns: int, mask_ptr: int = 0, scores_ptr: int = 0, top1_ptr: int = 0,
-                    numa_ptr: int = 0) -> None:
+                    numa_ptr: int = 0, rsv_ptr: int = 0) -> None:
+        """Matrix mode into caller-owned device buffers (16-byte aligned, any previous content: every requested
+        plane is written whole over its in-range cells and the mask's pad bits); asynchronous on the engine stream."""
         out = nat.EvalOut()
         out.mask, out.scores, out.top1, out.out_on_device = mask_ptr or None, scores_ptr or None, top1_ptr or None, 1
-        out.numa_scores = numa_ptr or None
+        out.numa_scores, out.rsv_scores = numa_ptr or None, rsv_ptr or None
         _check(nat.lib().kg_eval(self._h, int(now_ns), ctypes.byref(out)), self, "kg_eval")
 
     @staticmethod
@@ -368,6 +370,17 @@ class Engine:
         _check(nat.lib().kg_cycle_one(self._h, nat.ptr(pod_row), int(now_ns), nat.CYCLE_COMMIT if commit else 0,
                                       ctypes.byref(eo) if eo is not None else None, ctypes.byref(out)), self,
                "kg_cycle_one")
+        return out
+
+    def cycle_one_device(self, pod_row: np.ndarray, now_ns: int, commit: bool = False, mask_ptr: int = 0,
+                         scores_ptr: int = 0, numa_ptr: int = 0, top1_ptr: int = 0) -> "nat.CycleOut":
+        """kg_cycle_one with the planes (and the top1 key) in caller-owned device buffers, as eval_device."""
+        out = nat.CycleOut()
+        eo = nat.EvalOut()
+        eo.mask, eo.scores, eo.numa_scores, eo.top1 = mask_ptr or None, scores_ptr or None, numa_ptr or None, top1_ptr or None
+        eo.out_on_device = 1
+        _check(nat.lib().kg_cycle_one(self._h, nat.ptr(pod_row), int(now_ns), nat.CYCLE_COMMIT if commit else 0,
+                                      ctypes.byref(eo), ctypes.byref(out)), self, "kg_cycle_one")
         return out
 
     # Reservation / ElasticQuota -----------------------------------------------------------
