@@ -670,6 +670,23 @@ kg_status kg_set_shard(kg_engine *eng, int32_t begin, int32_t end);
 /* Pod batch (uploaded once; HBM-resident until replaced). */
 kg_status kg_pods_set(kg_engine *eng, const kg_pod_row *pods, int32_t n_pods);
 
+/* The slot map kg_pods_set chooses for a batch (host only, no engine): the resources the fp64 slot kernels carry.
+ * A pod "needs" a resource when the Fit filter compares it (a native with a non-zero request, a scalar whose key
+ * is present) or NodeResourcesFit scores it (weighted, and for a scalar a non-zero score request).  Over the union
+ * of the pods' needs:
+ *   - within {cpu, memory}: 2 slots; within {cpu, memory, batch-cpu, batch-memory}: those 4 slots;
+ *   - at most 8 resources: 8 slots, cpu and memory then the others in ascending resource id (unused slots −1);
+ *   - more than 8: cpu, memory and the 6 other resources that the most pods need (ties to the lower resource id),
+ *     stored in ascending resource id.  A pod that needs a resource outside the map is a spill pod (spill[i] = 1;
+ *     a pod that alone needs more than 8 always is): the engine evaluates it on the generic pair path, which
+ *     answers all KG_NUM_RES resources, so its results do not depend on the map.
+ * The rule is deterministic.  n_slots ← 2, 4 or 8; slot_res[8] ← resource id per slot; spill (n bytes, may be
+ * NULL) ← 0 / 1 per pod, all zero unless the union exceeds 8. */
+kg_status kg_batch_slot_map(const kg_config *cfg, const kg_pod_row *pods, int32_t n, int32_t *n_slots,
+                            int32_t slot_res[8], uint8_t *spill);
+/* Spill pods of the batch uploaded with kg_pods_set (0 for every batch of at most 8 resources). */
+int32_t kg_pods_spill_count(const kg_engine *eng);
+
 /* Matrix mode: every (pod, node) Filter+Score of the uploaded batch against the snapshot. */
 kg_status kg_eval(kg_engine *eng, int64_t now_ns, const kg_eval_out *out);
 

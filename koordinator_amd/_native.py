@@ -234,7 +234,7 @@ EXPORTED = [
     "kg_snapshot_generation", "kg_cpuset_take", "kg_row_reserve", "kg_cpus_set", "kg_cpus_download",
     "kg_place_chunk_resolve_prev", "kg_set_eval_stream", "kg_set_forms", "kg_comm_unique_id", "kg_comm_init",
     "kg_place_sharded", "kg_counters_get", "kg_counters_reset", "kg_comm_init_loopback", "kg_comm_kind",
-    "kg_cycle_one",
+    "kg_cycle_one", "kg_batch_slot_map", "kg_pods_spill_count",
 ]
 
 _lib = None
@@ -286,6 +286,7 @@ def lib() -> ctypes.CDLL:
         "kg_place_sharded": (i32, [vp, ctypes.c_int64, vp, vp]), "kg_counters_get": (i32, [vp, vp]), "kg_counters_reset": (i32, [vp]),
         "kg_comm_init_loopback": (i32, [vp, i32, i32, ctypes.c_char_p]), "kg_comm_kind": (i32, [vp]),
         "kg_cycle_one": (i32, [vp, vp, i64, ctypes.c_uint32, vp, vp]),
+        "kg_batch_slot_map": (i32, [vp, vp, i32, vp, vp, vp]), "kg_pods_spill_count": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         if host_only and not hasattr(L, name):

@@ -78,6 +78,7 @@
 //   94-95 k_rsv_reduce                top1, Reservation plane (rsv_best_block)
 //   96-98 k_quota_apply               mask words, Reservation plane, top1
 //   99-100 k_eq_rows                  distinct row (read), output row vector
+//   101-105 k_eval_spill              listed pod (read), score pairs, mask words, tile keys, top-k tile keys
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -1358,6 +1359,110 @@ __global__ __launch_bounds__(256) void k_eval_exact(kg_consts c, kg_planes pl, c
         key = wave_max_u32(key);
         if ((threadIdx.x & 63) == 0 && key && KG_IN2(77, p, n_pods, node / KG_TILE, tiles_total))
             atomicMax(&partials[(int64_t)p * tiles_total + node / KG_TILE], key);
+    }
+}
+
+// Spill pods (kg_batch_slot_map: pods that compare or score a resource outside the batch's 8-slot map): k_eval2
+// answers them from a hot row that lacks that resource, so this kernel, launched right after it, evaluates them
+// from their kg_pod_dev rows on the generic pair path (eval_pair answers every resource: the fp64 planes below
+// KG_FAST_RES, kg_pair_exact above, slow nodes, LoadAware extra weights) and overwrites what k_eval2 wrote for
+// them, in k_eval2's own layouts: OUT the 64-column mask words (the wave ballots, plain stores), the score pairs
+// and the tile's best key; TOPK (placement chunks) the tile's KG_TOPK best keys; neither: the tile key alone.
+// One workgroup = one tile × a group of the listed pods, two nodes per lane as k_eval2 (so the column / partial
+// last tile / col_begin handling is k_eval2's): the tile's node registers are loaded once and serve every pod
+// of the group, whose rows are staged KG_SPILL_CHUNK at a time in LDS (wave-uniform reads).  A placement chunk
+// leaves slow nodes out, as k_eval2 does (the resolve re-scores the slow list itself).  `list`: ascending pod
+// indices of the batch, of which pod_begin is output row 0.  XCD-aware order (k_eval_numa_chunk): the groups of
+// one tile are consecutive workgroups of one XCD, whose L2 serves the tile's planes and rows to all of them.
+#define KG_SPILL_CHUNK 8   // pods per LDS pass (TOPK: 8 × 1024 keys = 32 KiB)
+template <bool OUT, bool TOPK>
+__global__ __launch_bounds__(KG_BLOCK) void k_eval_spill(kg_consts c, kg_planes pl, HotArgs a,
+                                                         const kg_pod_dev *__restrict__ pods,
+                                                         const int32_t *__restrict__ list, int32_t n_list,
+                                                         int32_t pod_begin, int32_t shard_tiles, int32_t n_groups,
+                                                         int32_t pods_per_group, unsigned long long *__restrict__ mask,
+                                                         uint16_t *__restrict__ scores, uint32_t *__restrict__ partials) {
+    static_assert(!(TOPK && OUT), "top-k partials are a placement-chunk mode");
+    __shared__ __attribute__((aligned(16))) kg_pod_dev lp[KG_SPILL_CHUNK];
+    __shared__ __attribute__((aligned(16))) uint32_t kbuf[KG_SPILL_CHUNK * KG_BLOCK * (TOPK ? 2 : 1)];
+    __shared__ int32_t lrow[KG_SPILL_CHUNK];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x, xcd = b % KG_XCDS, r = b / KG_XCDS;
+    const int tile_rel = (r / n_groups) * KG_XCDS + xcd, group = r % n_groups;
+    if (tile_rel >= shard_tiles) return;   // grid padded to a multiple of 8 tiles; block-uniform
+    const int tile = a.tile_begin + tile_rel;
+    const int64_t wave_base = (int64_t)tile * KG_TILE + wave * 128;
+    const int64_t node0 = wave_base + lane, node1 = node0 + 64;
+    const bool in0 = node0 < a.node_end, in1 = node1 < a.node_end;
+    const BatchMasks bm{0xFFu, 0xFFu};
+    NodeRegs n0, n1;
+    load_node(c, pl, node0, in0, bm, a.now_ns, n0);
+    load_node(c, pl, node1, in1, bm, a.now_ns, n1);
+    // (a placement chunk's lists carry no slow node)
+    const bool use0 = in0 && !(TOPK && (n0.df & KGD_SLOW)), use1 = in1 && !(TOPK && (n1.df & KGD_SLOW));
+    // output columns: a 64-node segment is written iff it lies inside the padded row (wave-uniform)
+    const int64_t col0 = wave_base - a.col_begin;
+    const bool seg0 = col0 < a.score_stride, seg1 = col0 + 64 < a.score_stride;
+    const int mask_lanes = seg1 ? 2 : seg0 ? 1 : 0;
+    const uint32_t local0 = (uint32_t)(wave * 128 + lane);
+    const uint32_t kb0 = (1u << KG_TILE_SHIFT) + (KG_TILE - 1) - local0, kb1 = kb0 - 64;
+    constexpr int POD_DW = (int)(sizeof(kg_pod_dev) / 4);
+    const int gb = group * pods_per_group;
+    const int ge = min(gb + pods_per_group, n_list);
+    for (int q0 = gb; q0 < ge; q0 += KG_SPILL_CHUNK) {
+        const int nq = min(KG_SPILL_CHUNK, ge - q0);
+        for (int k = tid; k < nq * POD_DW; k += KG_BLOCK) {
+            const int j = k / POD_DW, w = k - j * POD_DW;
+            const int32_t p = list[q0 + j] - pod_begin;
+            reinterpret_cast<uint32_t *>(&lp[j])[w] =
+                KG_IN(101, p, a.n_pods) ? reinterpret_cast<const uint32_t *>(pods + p)[w] : 0u;
+        }
+        if (tid < nq) lrow[tid] = list[q0 + tid] - pod_begin;
+        __syncthreads();
+        for (int j = 0; j < nq; j++) {
+            const int p = __builtin_amdgcn_readfirstlane(lrow[j]);
+            uint32_t fit0 = 0, la0 = 0, fit1 = 0, la1 = 0;
+            const bool ok0 = use0 && eval_pair(c, pl, lp[j], n0, node0, a.now_ns, fit0, la0);
+            const bool ok1 = use1 && eval_pair(c, pl, lp[j], n1, node1, a.now_ns, fit1, la1);
+            if (OUT) {
+                uint16_t *s = scores + (int64_t)p * a.score_stride + col0 + lane;
+                if (seg0 && KG_IN2(102, p, a.n_pods, col0 + lane, a.score_stride)) s[0] = (uint16_t)(fit0 | (la0 << 8));
+                if (seg1 && KG_IN2(102, p, a.n_pods, col0 + 64 + lane, a.score_stride)) s[64] = (uint16_t)(fit1 | (la1 << 8));
+                const unsigned long long b0 = __ballot(ok0), b1 = __ballot(ok1);
+                if (lane < mask_lanes && KG_IN2(103, p, a.n_pods, (col0 >> 6) + lane, a.mask_words))
+                    mask[(int64_t)p * a.mask_words + (col0 >> 6) + lane] = lane ? b1 : b0;
+            }
+            const uint32_t k0 = ok0 ? (total_of(c, fit0, la0) << KG_TILE_SHIFT) + kb0 : 0u;
+            const uint32_t k1 = ok1 ? (total_of(c, fit1, la1) << KG_TILE_SHIFT) + kb1 : 0u;
+            if (TOPK) {   // every key of the tile: [pod][1024], node-local order irrelevant
+                kbuf[j * 2 * KG_BLOCK + tid] = k0;
+                kbuf[j * 2 * KG_BLOCK + KG_BLOCK + tid] = k1;
+            } else {
+                kbuf[j * KG_BLOCK + tid] = k0 > k1 ? k0 : k1;
+            }
+        }
+        __syncthreads();
+        for (int j = wave; j < nq; j += KG_BLOCK / 64) {   // a wave per pod
+            const int p = __builtin_amdgcn_readfirstlane(lrow[j]);
+            if (TOPK) {
+                const uint32_t t = tile_topk(kbuf + j * 2 * KG_BLOCK);
+                if (lane < KG_TOPK && KG_IN2(105, p, a.n_pods, tile, a.tiles_total))
+                    partials[((int64_t)p * a.tiles_total + tile) * KG_PARTIAL_SLOTS + lane] = t;
+            } else {
+                uint32_t mx = 0;
+#pragma unroll
+                for (int i = 0; i < KG_BLOCK / 64; i++) {
+                    const uint32_t v = kbuf[j * KG_BLOCK + lane + 64 * i];
+                    mx = mx > v ? mx : v;
+                }
+                mx = wave_max_u32(mx);
+                if (lane == 0 && KG_IN2(104, p, a.n_pods, tile, a.tiles_total))
+                    partials[(int64_t)p * a.tiles_total + tile] = mx;
+            }
+        }
+        __syncthreads();
     }
 }
 
@@ -3075,6 +3180,11 @@ struct kg_engine {
     kg_pod_dev *eq_pods = nullptr;     // [eq_n]
     void *eq_hot = nullptr;            // [eq_n] their hot rows (the batch's slot map), for the Fit + LoadAware pass
     bool reps_in = false;              // pods / hot hold the distinct rows (eval_eq, ncache_build)
+    // spill pods (kg_batch_slot_map): ascending pod indices of the batch, and of the distinct rows when eq_on, whose
+    // hot rows lack a resource; k_eval_spill re-evaluates them after every slot-kernel launch (launch_spill)
+    std::vector<int32_t> spill_h, eq_spill_h;
+    int32_t *spill_list = nullptr, *eq_spill_list = nullptr;   // device copies
+    size_t spill_cap = 0, eq_spill_cap = 0;                      // their capacities (entries)
     int32_t *eq_perm = nullptr;        // [eq_n] their NodeNUMAResource visiting order (as numa_perm)
     bool eq_perm_on = false;
     int32_t *eq_of = nullptr;          // [n_pods] the distinct row of each pod
@@ -3755,6 +3865,45 @@ kg_status slow_refresh(kg_engine *e) {
     return KG_OK;
 }
 
+// The spill pods among pods [pod_begin, pod_begin + n) (kg_batch_slot_map), re-evaluated on the generic pair path
+// over what the slot kernel just wrote for them (k_eval_spill); nothing is launched when the range holds none,
+// so a batch of at most 8 resources issues the launches it always did.  Its own profiled interval under `prof`.
+kg_status launch_spill(kg_engine *e, int32_t pod_begin, int32_t n, uint64_t *mask, uint16_t *scores, uint32_t *partials,
+                       bool topk, const HotArgs &a, int64_t shard_tiles, bool prof) {
+    const std::vector<int32_t> &sh = e->reps_in ? e->eq_spill_h : e->spill_h;
+    if (sh.empty()) return KG_OK;
+    const int64_t lo = std::lower_bound(sh.begin(), sh.end(), pod_begin) - sh.begin();
+    const int64_t hi = std::lower_bound(sh.begin(), sh.end(), pod_begin + n) - sh.begin();
+    const int64_t ns = hi - lo;
+    if (ns <= 0) return KG_OK;
+    const int32_t *list = (e->reps_in ? e->eq_spill_list : e->spill_list) + lo;
+    // pods per workgroup: whole LDS passes, and about 2048 workgroups on a large launch (8 per CU in flight or
+    // queued), so the tile's node registers serve at least KG_SPILL_CHUNK pods
+    int64_t ppg = (ns * shard_tiles + 2047) / 2048;
+    ppg = (ppg + KG_SPILL_CHUNK - 1) / KG_SPILL_CHUNK * KG_SPILL_CHUNK;
+    if (ppg < KG_SPILL_CHUNK) ppg = KG_SPILL_CHUNK;
+    const int64_t groups = (ns + ppg - 1) / ppg;
+    const int64_t blocks = (shard_tiles + KG_XCDS - 1) / KG_XCDS * KG_XCDS * groups;
+    if (blocks > INT32_MAX) return set_err(e, KG_ERR_RANGE, "spill launch too large");
+    if (prof && e->profiling) HIP_TRY(e, prof_begin(e));
+    const dim3 grid((unsigned)blocks), block(KG_BLOCK);
+    if (mask)
+        hipLaunchKernelGGL((k_eval_spill<true, false>), grid, block, 0, e->stream, e->consts, e->pl, a, e->pods + pod_begin,
+                           list, (int32_t)ns, pod_begin, (int32_t)shard_tiles, (int32_t)groups, (int32_t)ppg,
+                           (unsigned long long *)mask, scores, partials);
+    else if (topk)
+        hipLaunchKernelGGL((k_eval_spill<false, true>), grid, block, 0, e->stream, e->consts, e->pl, a, e->pods + pod_begin,
+                           list, (int32_t)ns, pod_begin, (int32_t)shard_tiles, (int32_t)groups, (int32_t)ppg,
+                           (unsigned long long *)mask, scores, partials);
+    else
+        hipLaunchKernelGGL((k_eval_spill<false, false>), grid, block, 0, e->stream, e->consts, e->pl, a, e->pods + pod_begin,
+                           list, (int32_t)ns, pod_begin, (int32_t)shard_tiles, (int32_t)groups, (int32_t)ppg,
+                           (unsigned long long *)mask, scores, partials);
+    HIP_TRY(e, hipGetLastError());
+    if (prof && e->profiling) HIP_TRY(e, prof_end(e));
+    return KG_OK;
+}
+
 // topk: placement chunk (partials of KG_PARTIAL_SLOTS per (pod, tile) on the non-NUMA path; the NUMA
 // kernel writes one key per (pod, tile), slot 0 of a dense [n][tiles] layout — see partial_slots)
 // Fit + LoadAware over the launch's pods (every form but NodeNUMAResource's): the LAX / exact forms for LoadAware
@@ -3796,6 +3945,10 @@ kg_status launch_eval_plain(kg_engine *e, int64_t now_ns, int32_t pod_begin, int
 #undef KG_LAX_LAUNCH
         HIP_TRY(e, hipGetLastError());
         if (prof && e->profiling) HIP_TRY(e, prof_end(e));
+        {
+            const kg_status st = launch_spill(e, pod_begin, n, mask, scores, partials, false, a, shard_tiles, prof);
+            if (st) return st;
+        }
         HIP_TRY(e, hipMemsetAsync(e->xslow_count, 0, sizeof(int32_t), e->stream));
         if (e->n_nodes > 0)
             hipLaunchKernelGGL(k_slow_list, dim3((unsigned)((e->n_nodes + 255) / 256)), dim3(256), 0, e->stream, e->pl.dflags,
@@ -3831,9 +3984,11 @@ kg_status launch_eval_plain(kg_engine *e, int64_t now_ns, int32_t pod_begin, int
     else launch_hot<8>(e, grid, a, pod_begin, mask, scores, partials, topk);
     HIP_TRY(e, hipGetLastError());
     if (prof && e->profiling) HIP_TRY(e, prof_end(e));
+    kg_status st = use_cls ? KG_OK : launch_spill(e, pod_begin, n, mask, scores, partials, topk, a, shard_tiles, prof);
+    if (st) return st;
     // exact re-evaluation of the (rare) nodes outside the fp64 fast-path bounds; a placement chunk
     // leaves them to the resolve, which re-scores the slow-node list itself
-    kg_status st = slow_refresh(e);
+    st = slow_refresh(e);
     if (st) return st;
     if (!topk) {
         hipLaunchKernelGGL(k_fix_slow, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->consts, e->pl,
@@ -4085,6 +4240,8 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->pods) (void)hipFree(e->pods);
     if (e->hot) (void)hipFree(e->hot);
     if (e->eq_hot) (void)hipFree(e->eq_hot);
+    if (e->spill_list) (void)hipFree(e->spill_list);
+    if (e->eq_spill_list) (void)hipFree(e->eq_spill_list);
     if (e->scratch) (void)hipFree(e->scratch);
     if (e->cls_mem) (void)hipFree(e->cls_mem);
     if (e->rsv_mem) (void)hipFree(e->rsv_mem);
@@ -4303,6 +4460,8 @@ kg_status kg_set_shard(kg_engine *e, int32_t begin, int32_t end) {
 
 int32_t kg_num_tiles(const kg_engine *e) { return e ? (int32_t)tiles_total(e) : 0; }
 
+int32_t kg_pods_spill_count(const kg_engine *e) { return e ? (int32_t)e->spill_h.size() : 0; }
+
 kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
     kg_status st = check_engine(e);
     if (st) return st;
@@ -4310,7 +4469,6 @@ kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
     std::vector<kg_pod_dev> dev((size_t)n);
     BatchMasks bm{0, 0};
     bool la_prod = false, pow2 = true, batch_bind = false;
-    uint32_t need = 0;
     int32_t max_quota = -1;
     for (int32_t i = 0; i < n; i++) {
         if (!kg_pod_row_in_bounds(rows[i])) return set_err(e, KG_ERR_RANGE, "pod %d: request outside the engine bounds", i);
@@ -4329,35 +4487,45 @@ kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
     if (!(e->cfg.enabled_plugins & KG_PLUGIN_FIT)) bm.cmp = bm.fit = 0;
     if (!(e->cfg.enabled_plugins & KG_PLUGIN_LOADAWARE)) la_prod = false;
     pow2 &= e->consts.la_shift != 0xFF || !(e->cfg.enabled_plugins & KG_PLUGIN_LOADAWARE);
-    // resource profile: the smallest slot set covering every resource the batch compares or scores
-    int32_t nslot;
+    // resource profile (kg_batch_slot_map): the smallest slot set covering every resource the batch compares or
+    // scores; past 8 resources the 8 most needed, and the pods that need another one are spill pods (k_eval_spill)
+    int32_t nslot = 2;
     int32_t slot_res[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    std::vector<uint8_t> spill((size_t)n);
+    if (kg_batch_slot_map(&e->cfg, rows, n, &nslot, slot_res, spill.data()) != KG_OK)
+        return set_err(e, KG_ERR_INVALID_ARG, "bad pod batch");
     std::vector<char> hot;
-    auto build = [&](auto tag, int ns, const int32_t *map) {
+    auto build = [&](auto tag) {
         using H = decltype(tag);
-        nslot = ns;
-        for (int s = 0; s < ns; s++) slot_res[s] = map[s];
         hot.assign(sizeof(H) * (size_t)n, 0);
-        need = 0;
-        for (int32_t i = 0; i < n; i++) need |= kg_pod_hot_from_row(e->cfg, rows[i], slot_res, ((H *)hot.data())[i]);
+        for (int32_t i = 0; i < n; i++) kg_pod_hot_from_row(e->cfg, rows[i], slot_res, ((H *)hot.data())[i]);
     };
-    static const int32_t native_map[2] = {KG_RES_CPU, KG_RES_MEMORY};
-    static const int32_t coloc_map[4] = {KG_RES_CPU, KG_RES_MEMORY, KG_RES_BATCH_CPU, KG_RES_BATCH_MEMORY};
-    build(kg_pod_hot_t<2>(), 2, native_map);
-    if (need & ~0x3u) build(kg_pod_hot_t<4>(), 4, coloc_map);
-    if (need & ~0x1Bu) {   // 8 slots: cpu, memory and every other resource the batch compares or scores (≤ 6 more)
-        int32_t map8[8] = {KG_RES_CPU, KG_RES_MEMORY, -1, -1, -1, -1, -1, -1};
-        int ns8 = 2;
-        for (int r = 2; r < KG_NUM_RES; r++) {
-            if (!((need >> r) & 1u)) continue;
-            if (ns8 == 8)
-                return set_err(e, KG_ERR_UNSUPPORTED, "the batch compares or scores more than 8 resources (%d)",
-                               __builtin_popcount(need | 3u));
-            map8[ns8++] = r;
+    if (nslot == 2) build(kg_pod_hot_t<2>());
+    else if (nslot == 4) build(kg_pod_hot_t<4>());
+    else build(kg_pod_hot_t<8>());
+    std::vector<int32_t> spill_h;
+    for (int32_t i = 0; i < n; i++)
+        if (spill[(size_t)i]) spill_h.push_back(i);
+    // (a device list grows on demand; a batch without spill pods allocates and copies nothing)
+    auto upload_spill = [&](const std::vector<int32_t> &l, int32_t *&dst, size_t &cap) -> hipError_t {
+        if (l.empty()) return hipSuccess;
+        if (l.size() > cap) {
+            if (dst) {
+                const hipError_t st = hipFree(dst);
+                if (st != hipSuccess) return st;
+            }
+            dst = nullptr;
+            cap = 0;
+            const hipError_t st = hipMalloc(&dst, sizeof(int32_t) * l.size());
+            if (st != hipSuccess) return st;
+            cap = l.size();
         }
-        build(kg_pod_hot_t<8>(), 8, map8);
-    }
+        return h2d(e, dst, l.data(), sizeof(int32_t) * l.size(), e->stream);
+    };
     HIP_TRY(e, hipStreamSynchronize(e->stream));
+    e->spill_h.clear();      // (set again below, once the list is on the device)
+    e->eq_spill_h.clear();
+    HIP_TRY(e, upload_spill(spill_h, e->spill_list, e->spill_cap));
     if (n > e->pods_cap || hot.size() > e->hot_bytes) {
         if (e->pods) HIP_TRY(e, hipFree(e->pods));
         if (e->hot) HIP_TRY(e, hipFree(e->hot));
@@ -4478,6 +4646,9 @@ kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
                 HIP_TRY(e, hipMalloc(&e->eq_hot, uh.size()));
                 HIP_TRY(e, h2d(e, e->eq_hot, uh.data(), uh.size(), e->stream));
             }
+            for (int32_t k = 0; k < u; k++)   // the distinct rows' spill list (reps ascend, so does it)
+                if (spill[(size_t)reps[(size_t)k]]) e->eq_spill_h.push_back(k);
+            HIP_TRY(e, upload_spill(e->eq_spill_h, e->eq_spill_list, e->eq_spill_cap));
             e->eq_perm_on = (e->cfg.enabled_plugins & KG_PLUGIN_NUMA) && u > 64;
             if (e->eq_perm_on) {
                 const std::vector<int32_t> order = numa_order(reps);
@@ -4488,6 +4659,7 @@ kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
         }
     }
     HIP_TRY(e, hipStreamSynchronize(e->stream));
+    e->spill_h = std::move(spill_h);
     e->nslot = nslot;
     for (int s = 0; s < 8; s++) e->slot_res[s] = slot_res[s];
     e->n_pods = n;

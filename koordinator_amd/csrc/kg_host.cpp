@@ -979,3 +979,50 @@ bool kg_pod_row_in_bounds(const kg_pod_row &row) {
     return row.la_estimate[0] >= 0 && row.la_estimate[0] < KG_VAL_LIMIT && row.la_estimate[1] >= 0 &&
            row.la_estimate[1] < KG_VAL_LIMIT;
 }
+
+// The batch's slot map (kg_batch_slot_map, koord_gpu.h): which resources the slot kernels (k_eval2) carry for the
+// batch, and which pods need a resource outside it (spill pods: evaluated on the generic pair path, k_eval_spill)
+extern "C" kg_status kg_batch_slot_map(const kg_config *cfg, const kg_pod_row *pods, int32_t n, int32_t *n_slots,
+                                       int32_t slot_res[8], uint8_t *spill) {
+    if (!cfg || n < 0 || (n > 0 && !pods) || !n_slots || !slot_res) return KG_ERR_INVALID_ARG;
+    static const int32_t native_map[2] = {KG_RES_CPU, KG_RES_MEMORY};
+    std::vector<uint32_t> need((size_t)n);
+    uint32_t uni = 0;
+    kg_pod_hot_t<2> scratch;
+    for (int32_t i = 0; i < n; i++) uni |= need[(size_t)i] = kg_pod_hot_from_row(*cfg, pods[i], native_map, scratch);
+    for (int s = 0; s < 8; s++) slot_res[s] = -1;
+    slot_res[0] = KG_RES_CPU;
+    slot_res[1] = KG_RES_MEMORY;
+    if (spill && n > 0) memset(spill, 0, (size_t)n);
+    if (!(uni & ~0x3u)) {
+        *n_slots = 2;
+        return KG_OK;
+    }
+    if (!(uni & ~0x1Bu)) {   // cpu, memory, batch-cpu, batch-memory
+        *n_slots = 4;
+        slot_res[2] = KG_RES_BATCH_CPU;
+        slot_res[3] = KG_RES_BATCH_MEMORY;
+        return KG_OK;
+    }
+    *n_slots = 8;
+    uint32_t others = uni & ~0x3u;
+    if (__builtin_popcount(others) > 6) {
+        // more than 8 resources: the 6 others most pods need (ties to the lower resource id)
+        int32_t count[KG_NUM_RES] = {};
+        for (int32_t i = 0; i < n; i++)
+            for (int r = 2; r < KG_NUM_RES; r++) count[r] += (int32_t)bit(need[(size_t)i], r);
+        others = 0;
+        for (int k = 0; k < 6; k++) {
+            int best = -1;
+            for (int r = 2; r < KG_NUM_RES; r++)
+                if (!bit(others, r) && count[r] > 0 && (best < 0 || count[r] > count[best])) best = r;
+            others |= 1u << best;   // (more than 6 resources have a count: best is one of them)
+        }
+    }
+    int ns = 2;
+    for (int r = 2; r < KG_NUM_RES; r++)
+        if (bit(others, r)) slot_res[ns++] = r;
+    if (spill)
+        for (int32_t i = 0; i < n; i++) spill[i] = (need[(size_t)i] & ~(others | 0x3u)) ? 1 : 0;
+    return KG_OK;
+}

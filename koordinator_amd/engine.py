@@ -85,6 +85,20 @@ def row_rsv_restore(cfg: np.ndarray, node_row: np.ndarray, rsv: np.ndarray, pod_
     return out
 
 
+def batch_slot_map(cfg: np.ndarray, pod_rows: np.ndarray):
+    """kg_batch_slot_map: the slot map set_pods chooses for the batch, on the host alone.  Returns (n_slots,
+    slot_res, spill): 2, 4 or 8; the resource id of each of the 8 slots (−1 unused); and a bool per pod, True for
+    the spill pods (pods that need a resource outside the map: only when the batch needs more than 8 resources)."""
+    rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+    n_slots = ctypes.c_int32(0)
+    slot_res = np.full(8, -1, dtype=np.int32)
+    spill = np.zeros(max(len(rows), 1), dtype=np.uint8)
+    _check(nat.lib().kg_batch_slot_map(nat.ptr(cfg), nat.ptr(rows) if len(rows) else None, len(rows),
+                                       ctypes.addressof(n_slots), nat.ptr(slot_res), nat.ptr(spill)),
+           what="kg_batch_slot_map")
+    return int(n_slots.value), slot_res, spill[:len(rows)].astype(bool)
+
+
 class Engine:
     """One engine = one GPU, one HIP stream, one HBM-resident node snapshot."""
 
@@ -188,6 +202,11 @@ class Engine:
         rows = np.ascontiguousarray(rows, dtype=nat.POD_ROW)
         _check(nat.lib().kg_pods_set(self._h, nat.ptr(rows), len(rows)), self, "kg_pods_set")
         self.n_pods = len(rows)
+
+    def spill_count(self) -> int:
+        """kg_pods_spill_count: pods of the uploaded batch outside its slot map (batch_slot_map), evaluated on the
+        generic pair path."""
+        return int(nat.lib().kg_pods_spill_count(self._h))
 
     # evaluation -------------------------------------------------------------------------
     @property
