@@ -35,6 +35,9 @@
  *                           plugin.go:311-476, scoring.go:42-203, nominator.go:76-135)
  *   kg_quota_set            ElasticQuota group state for its PreFilter / Reserve (elasticquota/plugin.go:210-255,
  *                           :323-337; core/group_quota_manager.go:613-650, :791-797)
+ *   kg_elig_set / _update   the node-only Filter verdicts of plugins the engine does not model (NodeAffinity /
+ *                           nodeSelector, TaintToleration, NodeName, NodeUnschedulable, ...) as per-class node masks
+ *                           (kg_pod_row.elig_class), ANDed into feasibility wherever the engine chooses a node
  *
  * Units follow k8s Quantity conversions used by the plugins: cpu-like resources
  * (KG_RES_CPU) in milli-units (Quantity.MilliValue), every other resource in
@@ -451,7 +454,8 @@ typedef struct kg_pod_row {
     int32_t rsv_owner_class;            /* kg_pod_spec.rsv_owner_class */
     int32_t rsv_affinity_class;         /* kg_pod_spec.rsv_affinity_class */
     int32_t quota;                      /* kg_pod_spec.quota */
-    int32_t _pad2;
+    int32_t elig_class;                 /* node eligibility class (kg_elig_set): 0 unrestricted; k ≥ 1: the pod may
+                                           only run on nodes of class k − 1.  kg_build_pod_rows writes 0 */
     int64_t la_estimate_x[KG_NUM_RES - 2]; /* EstimatePod(pod)[r] for r = 2..11 (0 unless resourceWeights name r) */
 } kg_pod_row;
 
@@ -522,7 +526,8 @@ typedef struct kg_engine kg_engine;
  * Columns cover the evaluated node range [B, E) (the shard; the whole snapshot by default),
  * W = ceil((E - B) / 64), column c ⇔ node B + c:
  *   mask     [P][W] uint64: bit (c % 64) of word c/64 ⇔ pod p feasible on node B + c
- *            (AND of every enabled Filter plugin)
+ *            (AND of every enabled Filter plugin and, for a pod with an elig_class, of its class:
+ *            kg_elig_set)
  *   scores   [P][64·W][2] uint8: {NodeResourcesFit score, LoadAwareScheduling score} ∈ [0,100]
  *            (0 where a plugin is disabled; row stride 64·W pairs).  Like the reference, where Score
  *            runs only on the nodes that passed Filter, a score is meaningful only where the pair's
@@ -580,7 +585,8 @@ kg_status kg_row_commit(const kg_config *cfg, kg_node_row *node, const kg_pod_ro
 /* Filter + Score of one (pod, node) pair on host rows, through the same per-pair code the kernels
  * run: the single-node checks of a scheduling cycle (RunFilterPluginsWithNominatedPods for one
  * node, preemption's SelectVictimsOnNode, framework_extender.go:354-372) without a device.
- * Scores are the plugin scores (0..100) of the enabled plugins, 0 otherwise. */
+ * Scores are the plugin scores (0..100) of the enabled plugins, 0 otherwise.  kg_row_eval and kg_row_eval_rsv
+ * take no engine and ignore kg_pod_row.elig_class (kg_elig_set): the caller applies the class itself. */
 kg_status kg_row_eval(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *pod, int64_t now_ns,
                       int32_t *feasible, int32_t *fit_score, int32_t *la_score, int32_t *numa_score);
 /* Reserve of a pod that may bind a cpuset, on host rows (NodeNUMAResource.Reserve, plugin.go:375-419):
@@ -686,6 +692,28 @@ kg_status kg_batch_slot_map(const kg_config *cfg, const kg_pod_row *pods, int32_
                             int32_t slot_res[8], uint8_t *spill);
 /* Spill pods of the batch uploaded with kg_pods_set (0 for every batch of at most 8 resources). */
 int32_t kg_pods_spill_count(const kg_engine *eng);
+
+/* Node eligibility classes: the verdicts of the Filter plugins the engine does not model (NodeAffinity /
+ * nodeSelector, TaintToleration, NodeName, NodeUnschedulable, ...), one bit per (class, node).  A pod row with
+ * elig_class = k ≥ 1 is feasible only on the nodes whose bit is set in class k − 1; the bit is ANDed into the
+ * pair's feasibility on every path where the engine chooses or reports a node (kg_eval's mask and top1, kg_place,
+ * kg_place_sharded, the chunk API, kg_cycle_one).  Plugin scores stay the pair's own (meaningful where the mask
+ * bit is set).  elig_class = 0 is unrestricted.
+ * kg_elig_set replaces the whole table: masks is [n_classes][ceil(n_nodes / 64)] uint64, bit (n % 64) of word
+ * n / 64 of a class's row ⇔ node n (global snapshot index, also under kg_set_shard) is eligible; bits past
+ * n_nodes are ignored.  n_classes = 0 drops the table.  n_nodes must be the snapshot size (KG_ERR_RANGE);
+ * without a snapshot KG_ERR_STATE.  kg_snapshot_reset drops the table; kg_snapshot_upsert / kg_snapshot_remove
+ * leave it alone.  Under kg_place_sharded every rank loads the same table.
+ * kg_elig_update sets (eligible[i] != 0) or clears the bit of nodes[i] in class cls, i < n: the node-event path.
+ * An out-of-range class or node returns KG_ERR_RANGE and changes nothing.
+ * A batch (or a kg_cycle_one pod) that names a class at or past the loaded count, or a negative one, makes
+ * kg_eval, kg_place, kg_place_sharded, the chunk entry points and kg_cycle_one return KG_ERR_RANGE before anything
+ * is launched or changed.  kg_commit(pod, node) does not check eligibility: the node is the caller's decision.
+ * kg_pods_restricted_count: pods of the uploaded batch with elig_class != 0 (they take the generic pair path,
+ * k_eval_elig, like spill pods; kg_pods_spill_count keeps counting the pods outside the slot map only). */
+kg_status kg_elig_set(kg_engine *eng, const uint64_t *masks, int32_t n_classes, int32_t n_nodes);
+kg_status kg_elig_update(kg_engine *eng, int32_t cls, const int32_t *nodes, const uint8_t *eligible, int32_t n);
+int32_t kg_pods_restricted_count(const kg_engine *eng);
 
 /* Matrix mode: every (pod, node) Filter+Score of the uploaded batch against the snapshot. */
 kg_status kg_eval(kg_engine *eng, int64_t now_ns, const kg_eval_out *out);

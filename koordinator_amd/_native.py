@@ -123,7 +123,7 @@ POD_ROW = np.dtype([
     ("request", "<i8", (NUM_RES,)), ("fit_score_request", "<i8", (NUM_RES,)), ("nonzero_request", "<i8", (2,)),
     ("la_estimate", "<i8", (2,)), ("request_present", "<u4"), ("flags", "<u4"),
     ("numa_request", "<i8", (NUM_RES,)), ("numa_request_present", "<u4"), ("cpu_bind", "<u4"),
-    ("rsv_owner_class", "<i4"), ("rsv_affinity_class", "<i4"), ("quota", "<i4"), ("_pad2", "<i4"),
+    ("rsv_owner_class", "<i4"), ("rsv_affinity_class", "<i4"), ("quota", "<i4"), ("elig_class", "<i4"),
     ("la_estimate_x", "<i8", (NUM_RES - 2,)),
 ], align=True)
 
@@ -234,7 +234,8 @@ EXPORTED = [
     "kg_snapshot_generation", "kg_cpuset_take", "kg_row_reserve", "kg_cpus_set", "kg_cpus_download",
     "kg_place_chunk_resolve_prev", "kg_set_eval_stream", "kg_set_forms", "kg_comm_unique_id", "kg_comm_init",
     "kg_place_sharded", "kg_counters_get", "kg_counters_reset", "kg_comm_init_loopback", "kg_comm_kind",
-    "kg_cycle_one", "kg_batch_slot_map", "kg_pods_spill_count",
+    "kg_cycle_one", "kg_batch_slot_map", "kg_pods_spill_count", "kg_elig_set", "kg_elig_update",
+    "kg_pods_restricted_count",
 ]
 
 _lib = None
@@ -287,6 +288,8 @@ def lib() -> ctypes.CDLL:
         "kg_comm_init_loopback": (i32, [vp, i32, i32, ctypes.c_char_p]), "kg_comm_kind": (i32, [vp]),
         "kg_cycle_one": (i32, [vp, vp, i64, ctypes.c_uint32, vp, vp]),
         "kg_batch_slot_map": (i32, [vp, vp, i32, vp, vp, vp]), "kg_pods_spill_count": (i32, [vp]),
+        "kg_elig_set": (i32, [vp, vp, i32, i32]), "kg_elig_update": (i32, [vp, i32, vp, vp, i32]),
+        "kg_pods_restricted_count": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         if host_only and not hasattr(L, name):

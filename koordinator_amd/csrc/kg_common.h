@@ -79,7 +79,7 @@ struct kg_pod_dev {
     int32_t rsv_owner;           // Reservation owner class (−1 none)
     int32_t rsv_aff;             // required reservation-affinity class (−1 none)
     int32_t quota;               // ElasticQuota group (−1 none)
-    uint32_t _pad2;
+    uint32_t elig;               // kg_pod_row.elig_class: 0 unrestricted, k ≥ 1 → eligibility class k − 1 (kg_elig_ok)
     int64_t la_est_x[KG_NUM_RES - 2]; // EstimatePod of resources 2..7 (LoadAware weights beyond cpu / memory)
 };
 
@@ -196,7 +196,22 @@ struct kg_planes {
     int32_t *rsv_of;     // [cap] index of the node in the reservation node list, −1 none (nullptr: no list)
     double *la_Rx;       // [KG_NUM_RES − 2][cap] LoadAware planes of resources 2..7 (nullptr: not kept)
     double *la_Fx;       // [2 variants][KG_NUM_RES − 2][cap]
+    // node eligibility classes (kg_elig_set; nullptr / 0: none loaded)
+    const unsigned long long *elig;   // [elig_classes][elig_stride] bit (n % 64) of word n / 64: node n is eligible
+    const uint16_t *elig_cnt;         // [elig_classes][elig_stride / 16] eligible nodes per 1024-node tile
+    int32_t elig_stride;              // words per class row: cap / 64 (whole tiles; the words past the snapshot are 0)
+    int32_t elig_classes;
 };
+
+// The pod's eligibility class (the Filter plugins outside the engine) on `node` (global index): ANDed into the
+// pair's feasibility, never into its scores.  The pod row is wave-uniform, so an unrestricted pod pays one scalar
+// branch.  A class past the table (the entry points refuse such a batch) is eligible nowhere.
+KG_HD bool kg_elig_ok(const kg_planes &pl, const kg_pod_dev &p, int64_t node) {
+    if (p.elig == 0) return true;
+    const uint32_t k = p.elig - 1u;
+    if (k >= (uint32_t)pl.elig_classes || node < 0 || (node >> 6) >= pl.elig_stride) return false;
+    return (pl.elig[(int64_t)k * pl.elig_stride + (node >> 6)] >> (node & 63)) & 1ull;
+}
 
 KG_HD int64_t kg_abs64(int64_t x) { return x < 0 ? -x : x; }
 

@@ -79,6 +79,8 @@
 //   96-98 k_quota_apply               mask words, Reservation plane, top1
 //   99-100 k_eq_rows                  distinct row (read), output row vector
 //   101-105 k_eval_spill              listed pod (read), score pairs, mask words, tile keys, top-k tile keys
+//   106-112 k_eval_elig               listed pod (read), eligibility words (read), tile count (read), score pairs,
+//                                     mask words, tile keys, top-k tile keys
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -279,14 +281,23 @@ __device__ __forceinline__ bool eval_fast(const kg_consts &c, const kg_pod_dev &
     return ok;
 }
 
-__device__ __forceinline__ bool eval_pair(const kg_consts &c, const kg_planes &pl, const kg_pod_dev &p,
-                                          const NodeRegs &n, int64_t node, int64_t now_ns, uint32_t &fit, uint32_t &la) {
+// (the engine plugins alone: k_eval_elig, which holds the pod's eligibility words in LDS, ANDs the bit itself)
+__device__ __forceinline__ bool eval_pair_plugins(const kg_consts &c, const kg_planes &pl, const kg_pod_dev &p,
+                                                  const NodeRegs &n, int64_t node, int64_t now_ns, uint32_t &fit,
+                                                  uint32_t &la) {
     if ((n.df & KGD_SLOW) || ((p.cmp_mask | p.fit_mask) >> KG_FAST_RES)) {   // (a later named slot: exact path)
         bool feas;
         kg_pair_exact(c, pl.rows[node], n.df, p, now_ns, feas, fit, la);
         return feas;
     }
     return eval_fast(c, p, n, fit, la);
+}
+// Feasibility is the AND of the engine plugins and the pod's eligibility class (kg_elig_ok); the scores are the
+// pair's own either way
+__device__ __forceinline__ bool eval_pair(const kg_consts &c, const kg_planes &pl, const kg_pod_dev &p,
+                                          const NodeRegs &n, int64_t node, int64_t now_ns, uint32_t &fit, uint32_t &la) {
+    const bool feas = eval_pair_plugins(c, pl, p, n, node, now_ns, fit, la);
+    return feas && kg_elig_ok(pl, p, node);
 }
 
 __device__ __forceinline__ uint32_t total_of(const kg_consts &c, uint32_t fit, uint32_t la, uint32_t numa = 0u) {
@@ -1319,6 +1330,7 @@ __global__ void k_fix_slow(kg_consts c, kg_planes pl, const kg_pod_dev *__restri
         bool feas;
         uint32_t fit, la;
         kg_pair_exact(c, pl.rows[node], pl.dflags[node], pods[p], now_ns, feas, fit, la);
+        feas = feas && kg_elig_ok(pl, pods[p], node);
         const int64_t col = node - col_begin;
         if (scores && KG_IN2(72, p, n_pods, col, score_stride)) scores[(int64_t)p * score_stride + col] = (uint16_t)(fit | (la << 8));
         if (feas) {
@@ -1347,6 +1359,7 @@ __global__ __launch_bounds__(256) void k_eval_exact(kg_consts c, kg_planes pl, c
         bool feas = false;
         uint32_t fit = 0, la = 0;
         if (own) kg_pair_exact(c, pl.rows[node], df, pods[p], now_ns, feas, fit, la);
+        feas = feas && kg_elig_ok(pl, pods[p], node);
         if (own && scores && KG_IN2(75, p, n_pods, col, score_stride)) scores[(int64_t)p * score_stride + col] = (uint16_t)(fit | (la << 8));
         const unsigned long long word = __builtin_amdgcn_ballot_w64(feas);
         if (mask && (threadIdx.x & 63) == 0 && (col >> 6) < mask_words && in && KG_IN2(76, p, n_pods, col >> 6, mask_words))
@@ -1459,6 +1472,193 @@ __global__ __launch_bounds__(KG_BLOCK) void k_eval_spill(kg_consts c, kg_planes 
                 }
                 mx = wave_max_u32(mx);
                 if (lane == 0 && KG_IN2(104, p, a.n_pods, tile, a.tiles_total))
+                    partials[(int64_t)p * a.tiles_total + tile] = mx;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Eligible nodes per (class, 1024-node tile) of classes [cls0, cls0 + n_cls): one wave per (class, tile) sums the
+// popcounts of the tile's 16 words (kg_elig_set: every class; kg_elig_update: the updated class)
+__global__ __launch_bounds__(64) void k_elig_count(const unsigned long long *__restrict__ table, int32_t stride,
+                                                   int32_t tiles, int32_t cls0, int32_t n_cls,
+                                                   uint16_t *__restrict__ cnt) {
+    const int64_t b = blockIdx.x;
+    if (b >= (int64_t)n_cls * tiles) return;   // block-uniform
+    const int32_t cls = cls0 + (int32_t)(b / tiles), tile = (int32_t)(b % tiles);
+    const int lane = threadIdx.x;
+    uint32_t v = lane < KG_TILE / 64 ? (uint32_t)__popcll(table[(int64_t)cls * stride + tile * (KG_TILE / 64) + lane]) : 0u;
+    for (int o = 8; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (lane == 0) cnt[(int64_t)cls * tiles + tile] = (uint16_t)v;
+}
+
+// Restricted pods (kg_pod_row.elig_class != 0: the Filter verdicts of plugins outside the engine, kg_elig_set):
+// the slot kernels know nothing of the class, so this kernel, launched after them (and after k_eval_spill, whose
+// list holds no restricted pod), answers the listed pods itself on the generic pair path (eval_pair_plugins: all
+// KG_NUM_RES resources, so a restricted pod outside the slot map needs no other kernel) ANDed with the class bit,
+// and overwrites what the slot kernel wrote for them.  k_eval_spill's geometry and layouts: one workgroup = one
+// tile × a group of the listed pods, two nodes per lane, pod rows staged KG_SPILL_CHUNK at a time in LDS, OUT /
+// TOPK / tile-key outputs as there.  What the class saves:
+//   - a (pod, tile) whose class has no eligible node in the tile (elig_cnt) evaluates nothing: mask words 0, tile
+//     key 0 (TOPK: the KG_TOPK keys 0);
+//   - a 64-node segment whose eligibility word is 0 evaluates nothing either: mask word 0, keys 0, and its score
+//     pairs stay the slot kernel's (meaningless where the mask bit is clear);
+//   - a workgroup whose pods all miss the tile (a first pass over the group's tile counts) writes those zeros and
+//     leaves without loading the tile's node registers.
+// The tile's 16 eligibility words and its count are staged in LDS once per run of pods of one class: the list of
+// a whole batch is sorted by class (launch_elig), so that is once per class and tile; a pod range's list ascends
+// by pod and restages where the class changes.
+template <bool OUT, bool TOPK>
+__global__ __launch_bounds__(KG_BLOCK) void k_eval_elig(kg_consts c, kg_planes pl, HotArgs a,
+                                                        const kg_pod_dev *__restrict__ pods,
+                                                        const int32_t *__restrict__ list, int32_t n_list,
+                                                        int32_t pod_begin, int32_t shard_tiles, int32_t n_groups,
+                                                        int32_t pods_per_group, unsigned long long *__restrict__ mask,
+                                                        uint16_t *__restrict__ scores, uint32_t *__restrict__ partials) {
+    static_assert(!(TOPK && OUT), "top-k partials are a placement-chunk mode");
+    __shared__ __attribute__((aligned(16))) kg_pod_dev lp[KG_SPILL_CHUNK];
+    __shared__ __attribute__((aligned(16))) uint32_t kbuf[KG_SPILL_CHUNK * KG_BLOCK * (TOPK ? 2 : 1)];
+    __shared__ int32_t lrow[KG_SPILL_CHUNK];
+    __shared__ int32_t lempty[KG_SPILL_CHUNK];              // the pod's class has no eligible node in the tile
+    __shared__ unsigned long long lew[KG_TILE / 64];        // the staged class's eligibility words of the tile
+    __shared__ uint32_t lcnt;                               // and its eligible-node count
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x, xcd = b % KG_XCDS, r = b / KG_XCDS;
+    const int tile_rel = (r / n_groups) * KG_XCDS + xcd, group = r % n_groups;
+    if (tile_rel >= shard_tiles) return;   // grid padded to a multiple of 8 tiles; block-uniform
+    const int tile = a.tile_begin + tile_rel;
+    const int64_t wave_base = (int64_t)tile * KG_TILE + wave * 128;
+    const int64_t node0 = wave_base + lane, node1 = node0 + 64;
+    const bool in0 = node0 < a.node_end, in1 = node1 < a.node_end;
+    constexpr int POD_DW = (int)(sizeof(kg_pod_dev) / 4);
+    constexpr int TW = KG_TILE / 64;   // eligibility words per tile
+    const int32_t cnt_tiles = pl.elig_stride / TW;
+    const int gb = group * pods_per_group;
+    const int ge = min(gb + pods_per_group, n_list);
+    // output columns: a 64-node segment is written iff it lies inside the padded row (wave-uniform)
+    const int64_t col0 = wave_base - a.col_begin;
+    const bool seg0 = col0 < a.score_stride, seg1 = col0 + 64 < a.score_stride;
+    const int mask_lanes = seg1 ? 2 : seg0 ? 1 : 0;
+    {   // does any pod of the group have an eligible node in the tile?  If none, the workgroup reads no plane
+        int need = 0;
+        for (int q = gb + tid; q < ge; q += KG_BLOCK) {
+            const int32_t p = list[q] - pod_begin;
+            const uint32_t cls = KG_IN(106, p, a.n_pods) ? pods[p].elig - 1u : 0xFFFFFFFFu;
+            if (cls < (uint32_t)pl.elig_classes && tile < cnt_tiles &&
+                KG_IN(108, (int64_t)cls * cnt_tiles + tile, (int64_t)pl.elig_classes * cnt_tiles))
+                need |= pl.elig_cnt[(int64_t)cls * cnt_tiles + tile] != 0;
+        }
+        if (!__syncthreads_or(need)) {
+            const int64_t word0 = ((int64_t)tile * KG_TILE - a.col_begin) >> 6;   // the tile's first mask word of a row
+            for (int q = gb + wave; q < ge; q += KG_BLOCK / 64) {   // a wave per pod
+                const int p = __builtin_amdgcn_readfirstlane(list[q] - pod_begin);
+                if (OUT && lane < TW && word0 + lane < a.mask_words && KG_IN2(110, p, a.n_pods, word0 + lane, a.mask_words))
+                    mask[(int64_t)p * a.mask_words + word0 + lane] = 0ull;
+                if (TOPK) {
+                    if (lane < KG_TOPK && KG_IN2(112, p, a.n_pods, tile, a.tiles_total))
+                        partials[((int64_t)p * a.tiles_total + tile) * KG_PARTIAL_SLOTS + lane] = 0u;
+                } else if (lane == 0 && KG_IN2(111, p, a.n_pods, tile, a.tiles_total)) {
+                    partials[(int64_t)p * a.tiles_total + tile] = 0u;
+                }
+            }
+            return;   // (block-uniform)
+        }
+    }
+    const BatchMasks bm{0xFFu, 0xFFu};
+    NodeRegs n0, n1;
+    load_node(c, pl, node0, in0, bm, a.now_ns, n0);
+    load_node(c, pl, node1, in1, bm, a.now_ns, n1);
+    // (a placement chunk's lists carry no slow node)
+    const bool use0 = in0 && !(TOPK && (n0.df & KGD_SLOW)), use1 = in1 && !(TOPK && (n1.df & KGD_SLOW));
+    const uint32_t local0 = (uint32_t)(wave * 128 + lane);
+    const uint32_t kb0 = (1u << KG_TILE_SHIFT) + (KG_TILE - 1) - local0, kb1 = kb0 - 64;
+    uint32_t cur_cls = 0xFFFFFFFFu;   // the class staged in lew / lcnt (none yet)
+    for (int q0 = gb; q0 < ge; q0 += KG_SPILL_CHUNK) {
+        const int nq = min(KG_SPILL_CHUNK, ge - q0);
+        for (int k = tid; k < nq * POD_DW; k += KG_BLOCK) {
+            const int j = k / POD_DW, w = k - j * POD_DW;
+            const int32_t p = list[q0 + j] - pod_begin;
+            reinterpret_cast<uint32_t *>(&lp[j])[w] =
+                KG_IN(106, p, a.n_pods) ? reinterpret_cast<const uint32_t *>(pods + p)[w] : 0u;
+        }
+        if (tid < nq) lrow[tid] = list[q0 + tid] - pod_begin;
+        __syncthreads();
+        for (int j = 0; j < nq; j++) {
+            const int p = __builtin_amdgcn_readfirstlane(lrow[j]);
+            const uint32_t cls = __builtin_amdgcn_readfirstlane(lp[j].elig) - 1u;   // (block-uniform)
+            if (cls != cur_cls) {
+                __syncthreads();   // the previous class's words have been read
+                const bool known = cls < (uint32_t)pl.elig_classes && tile < cnt_tiles;
+                if (tid < TW)
+                    lew[tid] = known && KG_IN(107, (int64_t)cls * pl.elig_stride + tile * TW + tid,
+                                              (int64_t)pl.elig_classes * pl.elig_stride)
+                                   ? pl.elig[(int64_t)cls * pl.elig_stride + tile * TW + tid]
+                                   : 0ull;
+                if (tid == 64)
+                    lcnt = known && KG_IN(108, (int64_t)cls * cnt_tiles + tile, (int64_t)pl.elig_classes * cnt_tiles)
+                               ? pl.elig_cnt[(int64_t)cls * cnt_tiles + tile]
+                               : 0u;
+                __syncthreads();
+                cur_cls = cls;
+            }
+            const uint32_t cnt = __builtin_amdgcn_readfirstlane(lcnt);
+            if (tid == 0) lempty[j] = cnt == 0;
+            if (cnt == 0) {   // no eligible node in the tile: nothing to evaluate
+                if (OUT && lane < mask_lanes && KG_IN2(110, p, a.n_pods, (col0 >> 6) + lane, a.mask_words))
+                    mask[(int64_t)p * a.mask_words + (col0 >> 6) + lane] = 0ull;
+                continue;
+            }
+            // the words of the wave's two 64-node segments (wave-uniform: scalar branches)
+            const unsigned long long w0 = lew[wave * 2], w1 = lew[wave * 2 + 1];
+            // (readfirstlane returns int: each half goes through uint32_t, or the low half's sign would fill the high one)
+            const uint32_t w0l = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w0);
+            const uint32_t w0h = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w0 >> 32));
+            const uint32_t w1l = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w1);
+            const uint32_t w1h = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w1 >> 32));
+            const unsigned long long e0 = ((unsigned long long)w0h << 32) | w0l, e1 = ((unsigned long long)w1h << 32) | w1l;
+            uint32_t fit0 = 0, la0 = 0, fit1 = 0, la1 = 0;
+            bool ok0 = false, ok1 = false;
+            if (e0) ok0 = use0 && eval_pair_plugins(c, pl, lp[j], n0, node0, a.now_ns, fit0, la0) && ((e0 >> lane) & 1ull);
+            if (e1) ok1 = use1 && eval_pair_plugins(c, pl, lp[j], n1, node1, a.now_ns, fit1, la1) && ((e1 >> lane) & 1ull);
+            if (OUT) {
+                uint16_t *s = scores + (int64_t)p * a.score_stride + col0 + lane;
+                if (e0 && seg0 && KG_IN2(109, p, a.n_pods, col0 + lane, a.score_stride)) s[0] = (uint16_t)(fit0 | (la0 << 8));
+                if (e1 && seg1 && KG_IN2(109, p, a.n_pods, col0 + 64 + lane, a.score_stride)) s[64] = (uint16_t)(fit1 | (la1 << 8));
+                const unsigned long long b0 = __ballot(ok0), b1 = __ballot(ok1);
+                if (lane < mask_lanes && KG_IN2(110, p, a.n_pods, (col0 >> 6) + lane, a.mask_words))
+                    mask[(int64_t)p * a.mask_words + (col0 >> 6) + lane] = lane ? b1 : b0;
+            }
+            const uint32_t k0 = ok0 ? (total_of(c, fit0, la0) << KG_TILE_SHIFT) + kb0 : 0u;
+            const uint32_t k1 = ok1 ? (total_of(c, fit1, la1) << KG_TILE_SHIFT) + kb1 : 0u;
+            if (TOPK) {   // every key of the tile: [pod][1024], node-local order irrelevant
+                kbuf[j * 2 * KG_BLOCK + tid] = k0;
+                kbuf[j * 2 * KG_BLOCK + KG_BLOCK + tid] = k1;
+            } else {
+                kbuf[j * KG_BLOCK + tid] = k0 > k1 ? k0 : k1;
+            }
+        }
+        __syncthreads();
+        for (int j = wave; j < nq; j += KG_BLOCK / 64) {   // a wave per pod
+            const int p = __builtin_amdgcn_readfirstlane(lrow[j]);
+            const bool empty = __builtin_amdgcn_readfirstlane(lempty[j]) != 0;
+            if (TOPK) {
+                const uint32_t t = empty ? 0u : tile_topk(kbuf + j * 2 * KG_BLOCK);
+                if (lane < KG_TOPK && KG_IN2(112, p, a.n_pods, tile, a.tiles_total))
+                    partials[((int64_t)p * a.tiles_total + tile) * KG_PARTIAL_SLOTS + lane] = t;
+            } else {
+                uint32_t mx = 0;
+                if (!empty) {
+#pragma unroll
+                    for (int i = 0; i < KG_BLOCK / 64; i++) {
+                        const uint32_t v = kbuf[j * KG_BLOCK + lane + 64 * i];
+                        mx = mx > v ? mx : v;
+                    }
+                    mx = wave_max_u32(mx);
+                }
+                if (lane == 0 && KG_IN2(111, p, a.n_pods, tile, a.tiles_total))
                     partials[(int64_t)p * a.tiles_total + tile] = mx;
             }
         }
@@ -2027,12 +2227,15 @@ __device__ __forceinline__ unsigned long long rsv_base_key(unsigned long long e,
 }
 
 // `row` / `df`: the node's canonical row and dflags (global, or the resolve's LDS copies)
+// (`nd`: the node's index; a node outside the pod's eligibility class is infeasible: e = 0, o = INT64_MAX, so it
+// is neither the preferred reservation node nor part of NormalizeScore's maximum)
 template <bool NUMA = true>
-__device__ __forceinline__ void rsv_entry(const kg_consts &c, const kg_node_row &row, uint32_t df, const RsvArgs &ra,
-                                          const kg_pod_dev &p, int32_t k, int64_t now_ns, kg_rsv_out *keep,
-                                          unsigned long long &e, int64_t &o) {
+__device__ __forceinline__ void rsv_entry(const kg_consts &c, const kg_planes &pl, int32_t nd, const kg_node_row &row,
+                                          uint32_t df, const RsvArgs &ra, const kg_pod_dev &p, int32_t k, int64_t now_ns,
+                                          kg_rsv_out *keep, unsigned long long &e, int64_t &o) {
     kg_rsv_out r;
     kg_rsv_pair<NUMA>(c, row, df, ra.rsv + ra.rfirst[k], ra.rfirst[k + 1] - ra.rfirst[k], p, now_ns, r);
+    r.feasible = r.feasible && kg_elig_ok(pl, p, nd);
     const uint32_t base = total_of(c, r.fit, r.la, r.numa);
     e = r.feasible ? ((unsigned long long)(base + 1u) << 32) | ((unsigned long long)r.raw << 16) |
                          (unsigned long long)(uint32_t)(r.nominated + 1)
@@ -2314,7 +2517,7 @@ __global__ __launch_bounds__(256) void k_rsv_eval(kg_consts c, kg_planes pl, Rsv
     const bool live = k < ra.n_rn;
     const int32_t nd = live ? ra.rnode[k] : 0;
     if (live) {
-        rsv_entry<NUMA>(c, pl.rows[nd], pl.dflags[nd], ra, pods[p], k, now_ns, &r, e, o);
+        rsv_entry<NUMA>(c, pl, nd, pl.rows[nd], pl.dflags[nd], ra, pods[p], k, now_ns, &r, e, o);
         ra.E[(int64_t)p * ra.n_rn + k] = e;
         ra.O[(int64_t)p * ra.n_rn + k] = o;
     }
@@ -2441,6 +2644,7 @@ __device__ __forceinline__ unsigned long long pair_key_cached(const kg_consts &c
     } else if (!eval_fast(c, p, n, fit, la)) {
         return 0ull;
     }
+    if (!kg_elig_ok(pl, p, node)) return 0ull;
     if (NUMA && (c.plugins & KG_PLUGIN_NUMA)) {
         const uint64_t ns = kg_numa_eval_any(c, crow, p);   // the LDS copy of the canonical row
         if (!(ns >> 32)) return 0ull;
@@ -2657,9 +2861,9 @@ __global__ __launch_bounds__(KG_RESOLVE_THREADS) void k_resolve(kg_consts c, kg_
                 const int32_t k = pl.rsv_of[nd];
                 if (k < 0) continue;
                 if (q < KG_NCACHE)   // the committed row and flags cached in LDS
-                    rsv_entry<NUMA>(c, nrow[q], ncache[q].n.df, ra, pd, k, now_ns, nullptr, E[k], O[k]);
+                    rsv_entry<NUMA>(c, pl, nd, nrow[q], ncache[q].n.df, ra, pd, k, now_ns, nullptr, E[k], O[k]);
                 else
-                    rsv_entry<NUMA>(c, pl.rows[nd], pl.dflags[nd], ra, pd, k, now_ns, nullptr, E[k], O[k]);
+                    rsv_entry<NUMA>(c, pl, nd, pl.rows[nd], pl.dflags[nd], ra, pd, k, now_ns, nullptr, E[k], O[k]);
             }
         }
         // a pod that requires a reservation can only land on reservation nodes (rsv part below)
@@ -3185,6 +3389,19 @@ struct kg_engine {
     std::vector<int32_t> spill_h, eq_spill_h;
     int32_t *spill_list = nullptr, *eq_spill_list = nullptr;   // device copies
     size_t spill_cap = 0, eq_spill_cap = 0;                      // their capacities (entries)
+    int32_t n_spill_width = 0;         // pods outside the slot map, restricted ones included (kg_pods_spill_count)
+    // restricted pods (elig_class != 0), of the batch and of the distinct rows when eq_on: k_eval_elig answers them
+    // after every slot-kernel launch (launch_elig) and they are kept off the spill lists.  Each list in two orders,
+    // [0, n) ascending pod index (a pod range's sub-list is contiguous) and [n, 2n) sorted by class then pod index
+    // (a launch over the whole list: the pods of a class share the staged eligibility words)
+    std::vector<int32_t> elig_h, eq_elig_h;            // the ascending order
+    int32_t *elig_list = nullptr, *eq_elig_list = nullptr;
+    size_t elig_cap = 0, eq_elig_cap = 0;
+    int32_t max_pod_elig = 0;          // the largest elig_class of the batch (INT32_MAX: a negative one), elig_ready
+    // the eligibility table (kg_elig_set): e->pl.elig / elig_cnt point into elig_mem; the host mirror serves
+    // kg_elig_update
+    void *elig_mem = nullptr;
+    std::vector<uint64_t> elig_host;   // [elig_classes][elig_stride]
     int32_t *eq_perm = nullptr;        // [eq_n] their NodeNUMAResource visiting order (as numa_perm)
     bool eq_perm_on = false;
     int32_t *eq_of = nullptr;          // [n_pods] the distinct row of each pod
@@ -3564,6 +3781,7 @@ void cls_prepare(kg_engine *e) {
     for (int32_t i = 0; i < (int32_t)e->pod_rows_h.size(); i++) {
         ClsKey k;
         if (!pod_class(e->cfg, e->pod_rows_h[i], k)) return;
+        if (e->pod_rows_h[i].elig_class != 0) return;   // a restricted pod: the batch takes the slot kernels + k_eval_elig
         auto it = index.find(k);
         int c;
         if (it == index.end()) {
@@ -3904,6 +4122,46 @@ kg_status launch_spill(kg_engine *e, int32_t pod_begin, int32_t n, uint64_t *mas
     return KG_OK;
 }
 
+// The restricted pods among pods [pod_begin, pod_begin + n) (elig_class != 0), answered by k_eval_elig over what the
+// slot kernel just wrote for them; nothing is launched when the range holds none, so a batch without restricted
+// pods issues the launches it always did.  Its own profiled interval under `prof`.
+kg_status launch_elig(kg_engine *e, int32_t pod_begin, int32_t n, uint64_t *mask, uint16_t *scores, uint32_t *partials,
+                      bool topk, const HotArgs &a, int64_t shard_tiles, bool prof) {
+    const std::vector<int32_t> &eh = e->reps_in ? e->eq_elig_h : e->elig_h;
+    if (eh.empty()) return KG_OK;
+    const int64_t lo = std::lower_bound(eh.begin(), eh.end(), pod_begin) - eh.begin();
+    const int64_t hi = std::lower_bound(eh.begin(), eh.end(), pod_begin + n) - eh.begin();
+    const int64_t ns = hi - lo;
+    if (ns <= 0) return KG_OK;
+    const int32_t *base = e->reps_in ? e->eq_elig_list : e->elig_list;
+    // the whole list: its class-sorted copy; a sub-range: the ascending one
+    const int32_t *list = ns == (int64_t)eh.size() ? base + eh.size() : base + lo;
+    // pods per workgroup as launch_spill: whole LDS passes, about 2048 workgroups on a large launch
+    int64_t ppg = (ns * shard_tiles + 2047) / 2048;
+    ppg = (ppg + KG_SPILL_CHUNK - 1) / KG_SPILL_CHUNK * KG_SPILL_CHUNK;
+    if (ppg < KG_SPILL_CHUNK) ppg = KG_SPILL_CHUNK;
+    const int64_t groups = (ns + ppg - 1) / ppg;
+    const int64_t blocks = (shard_tiles + KG_XCDS - 1) / KG_XCDS * KG_XCDS * groups;
+    if (blocks > INT32_MAX) return set_err(e, KG_ERR_RANGE, "eligibility launch too large");
+    if (prof && e->profiling) HIP_TRY(e, prof_begin(e));
+    const dim3 grid((unsigned)blocks), block(KG_BLOCK);
+    if (mask)
+        hipLaunchKernelGGL((k_eval_elig<true, false>), grid, block, 0, e->stream, e->consts, e->pl, a, e->pods + pod_begin,
+                           list, (int32_t)ns, pod_begin, (int32_t)shard_tiles, (int32_t)groups, (int32_t)ppg,
+                           (unsigned long long *)mask, scores, partials);
+    else if (topk)
+        hipLaunchKernelGGL((k_eval_elig<false, true>), grid, block, 0, e->stream, e->consts, e->pl, a, e->pods + pod_begin,
+                           list, (int32_t)ns, pod_begin, (int32_t)shard_tiles, (int32_t)groups, (int32_t)ppg,
+                           (unsigned long long *)mask, scores, partials);
+    else
+        hipLaunchKernelGGL((k_eval_elig<false, false>), grid, block, 0, e->stream, e->consts, e->pl, a, e->pods + pod_begin,
+                           list, (int32_t)ns, pod_begin, (int32_t)shard_tiles, (int32_t)groups, (int32_t)ppg,
+                           (unsigned long long *)mask, scores, partials);
+    HIP_TRY(e, hipGetLastError());
+    if (prof && e->profiling) HIP_TRY(e, prof_end(e));
+    return KG_OK;
+}
+
 // topk: placement chunk (partials of KG_PARTIAL_SLOTS per (pod, tile) on the non-NUMA path; the NUMA
 // kernel writes one key per (pod, tile), slot 0 of a dense [n][tiles] layout — see partial_slots)
 // Fit + LoadAware over the launch's pods (every form but NodeNUMAResource's): the LAX / exact forms for LoadAware
@@ -3946,7 +4204,8 @@ kg_status launch_eval_plain(kg_engine *e, int64_t now_ns, int32_t pod_begin, int
         HIP_TRY(e, hipGetLastError());
         if (prof && e->profiling) HIP_TRY(e, prof_end(e));
         {
-            const kg_status st = launch_spill(e, pod_begin, n, mask, scores, partials, false, a, shard_tiles, prof);
+            kg_status st = launch_spill(e, pod_begin, n, mask, scores, partials, false, a, shard_tiles, prof);
+            if (!st) st = launch_elig(e, pod_begin, n, mask, scores, partials, false, a, shard_tiles, prof);
             if (st) return st;
         }
         HIP_TRY(e, hipMemsetAsync(e->xslow_count, 0, sizeof(int32_t), e->stream));
@@ -3985,6 +4244,7 @@ kg_status launch_eval_plain(kg_engine *e, int64_t now_ns, int32_t pod_begin, int
     HIP_TRY(e, hipGetLastError());
     if (prof && e->profiling) HIP_TRY(e, prof_end(e));
     kg_status st = use_cls ? KG_OK : launch_spill(e, pod_begin, n, mask, scores, partials, topk, a, shard_tiles, prof);
+    if (!st && !use_cls) st = launch_elig(e, pod_begin, n, mask, scores, partials, topk, a, shard_tiles, prof);   // (cls_ok: no restricted pod)
     if (st) return st;
     // exact re-evaluation of the (rare) nodes outside the fp64 fast-path bounds; a placement chunk
     // leaves them to the resolve, which re-scores the slow-node list itself
@@ -4170,6 +4430,15 @@ kg_status quota_ready(kg_engine *e) {
     return KG_OK;
 }
 
+// every elig_class of the batch names a loaded class (checked at use, as quota_ready: the table may be replaced
+// or dropped between kg_pods_set and the evaluation)
+kg_status elig_ready(kg_engine *e) {
+    if (e->max_pod_elig > e->pl.elig_classes)
+        return set_err(e, KG_ERR_RANGE, "a pod's elig_class is outside the loaded eligibility classes (have %d: kg_elig_set)",
+                       e->pl.elig_classes);
+    return KG_OK;
+}
+
 // entries of pods [pod_begin, pod_begin + n) (n ≤ KG_RSV_POD_CHUNK) for every reservation node
 // split: also the placement split of the entries (RsvArgs::M / Mn / G) for the resolve
 kg_status rsv_eval_chunk(kg_engine *e, int64_t now_ns, int32_t pod_begin, int32_t n, uint64_t *mask, uint16_t *scores,
@@ -4242,6 +4511,9 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->eq_hot) (void)hipFree(e->eq_hot);
     if (e->spill_list) (void)hipFree(e->spill_list);
     if (e->eq_spill_list) (void)hipFree(e->eq_spill_list);
+    if (e->elig_list) (void)hipFree(e->elig_list);
+    if (e->eq_elig_list) (void)hipFree(e->eq_elig_list);
+    if (e->elig_mem) (void)hipFree(e->elig_mem);
     if (e->scratch) (void)hipFree(e->scratch);
     if (e->cls_mem) (void)hipFree(e->cls_mem);
     if (e->rsv_mem) (void)hipFree(e->rsv_mem);
@@ -4358,6 +4630,12 @@ kg_status kg_snapshot_reset(kg_engine *e, int32_t n_nodes) {
     e->rsv_g = nullptr;
     e->n_rsv = e->n_rn = 0;
     e->rsv_perm.clear();
+    if (e->elig_mem) HIP_TRY(e, hipFree(e->elig_mem));  // eligibility classes refer to node indices: dropped
+    e->elig_mem = nullptr;
+    e->elig_host.clear();
+    e->pl.elig = nullptr;
+    e->pl.elig_cnt = nullptr;
+    e->pl.elig_stride = e->pl.elig_classes = 0;
     e->pl.cap = cap;
     e->n_nodes = n_nodes;
     e->node_bind_facts.assign((size_t)n_nodes, 0);
@@ -4460,7 +4738,78 @@ kg_status kg_set_shard(kg_engine *e, int32_t begin, int32_t end) {
 
 int32_t kg_num_tiles(const kg_engine *e) { return e ? (int32_t)tiles_total(e) : 0; }
 
-int32_t kg_pods_spill_count(const kg_engine *e) { return e ? (int32_t)e->spill_h.size() : 0; }
+int32_t kg_pods_spill_count(const kg_engine *e) { return e ? e->n_spill_width : 0; }
+
+int32_t kg_pods_restricted_count(const kg_engine *e) { return e ? (int32_t)e->elig_h.size() : 0; }
+
+kg_status kg_elig_set(kg_engine *e, const uint64_t *masks, int32_t n_classes, int32_t n_nodes) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (n_classes < 0 || (n_classes > 0 && !masks)) return set_err(e, KG_ERR_INVALID_ARG, "bad eligibility table");
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised (kg_snapshot_reset)");
+    if (n_nodes != e->n_nodes) return set_err(e, KG_ERR_RANGE, "eligibility table of %d nodes, snapshot of %lld", n_nodes, (long long)e->n_nodes);
+    if (n_classes > (1 << 20)) return set_err(e, KG_ERR_RANGE, "too many eligibility classes (%d)", n_classes);
+    const int64_t stride = e->pl.cap / 64, tiles = e->pl.cap / KG_TILE, in_words = ((int64_t)n_nodes + 63) / 64;
+    // whole tiles per class row; the bits past the snapshot are cleared here, so callers need not zero them
+    std::vector<uint64_t> host((size_t)n_classes * (size_t)stride, 0);
+    for (int32_t k = 0; k < n_classes; k++) {
+        uint64_t *row = host.data() + (size_t)k * (size_t)stride;
+        if (in_words) memcpy(row, masks + (size_t)k * (size_t)in_words, (size_t)in_words * 8);
+        if (n_nodes % 64) row[in_words - 1] &= (1ull << (n_nodes % 64)) - 1ull;
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (e->eval_stream) HIP_TRY(e, hipStreamSynchronize(e->eval_stream));
+    if (e->elig_mem) HIP_TRY(e, hipFree(e->elig_mem));
+    e->elig_mem = nullptr;
+    e->elig_host.clear();
+    e->pl.elig = nullptr;
+    e->pl.elig_cnt = nullptr;
+    e->pl.elig_stride = e->pl.elig_classes = 0;
+    if (n_classes == 0) return KG_OK;
+    const size_t tab_b = (host.size() * 8 + 255) / 256 * 256, cnt_b = (size_t)n_classes * (size_t)tiles * 2;
+    HIP_TRY(e, hipMalloc(&e->elig_mem, tab_b + cnt_b));
+    unsigned long long *tab = (unsigned long long *)e->elig_mem;
+    uint16_t *cnt = (uint16_t *)((char *)e->elig_mem + tab_b);
+    HIP_TRY(e, h2d(e, tab, host.data(), host.size() * 8, e->stream));
+    const int64_t blocks = (int64_t)n_classes * tiles;
+    hipLaunchKernelGGL(k_elig_count, dim3((unsigned)blocks), dim3(64), 0, e->stream, tab, (int32_t)stride, (int32_t)tiles, 0,
+                       n_classes, cnt);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    e->elig_host = std::move(host);
+    e->pl.elig = tab;
+    e->pl.elig_cnt = cnt;
+    e->pl.elig_stride = (int32_t)stride;
+    e->pl.elig_classes = n_classes;
+    return KG_OK;
+}
+
+kg_status kg_elig_update(kg_engine *e, int32_t cls, const int32_t *nodes, const uint8_t *eligible, int32_t n) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (n < 0 || (n > 0 && (!nodes || !eligible))) return set_err(e, KG_ERR_INVALID_ARG, "bad eligibility update");
+    if (cls < 0 || cls >= e->pl.elig_classes) return set_err(e, KG_ERR_RANGE, "eligibility class %d out of range (have %d)", cls, e->pl.elig_classes);
+    for (int32_t i = 0; i < n; i++)
+        if (nodes[i] < 0 || nodes[i] >= e->n_nodes) return set_err(e, KG_ERR_RANGE, "node index %d out of range", nodes[i]);
+    if (n == 0) return KG_OK;
+    const int64_t stride = e->pl.elig_stride, tiles = stride / (KG_TILE / 64);
+    uint64_t *row = e->elig_host.data() + (size_t)cls * (size_t)stride;
+    for (int32_t i = 0; i < n; i++) {
+        const uint64_t bit = 1ull << (nodes[i] & 63);
+        if (eligible[i]) row[nodes[i] >> 6] |= bit;
+        else row[nodes[i] >> 6] &= ~bit;
+    }
+    // the class's row again (n_nodes / 8 bytes) and its tile counts; evaluations in flight finish first
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (e->eval_stream) HIP_TRY(e, hipStreamSynchronize(e->eval_stream));
+    unsigned long long *tab = (unsigned long long *)e->elig_mem;
+    HIP_TRY(e, h2d(e, tab + (size_t)cls * (size_t)stride, row, (size_t)stride * 8, e->stream));
+    hipLaunchKernelGGL(k_elig_count, dim3((unsigned)tiles), dim3(64), 0, e->stream, tab, (int32_t)stride, (int32_t)tiles, cls,
+                       1, const_cast<uint16_t *>(e->pl.elig_cnt));
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return KG_OK;
+}
 
 kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
     kg_status st = check_engine(e);
@@ -4503,9 +4852,27 @@ kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
     if (nslot == 2) build(kg_pod_hot_t<2>());
     else if (nslot == 4) build(kg_pod_hot_t<4>());
     else build(kg_pod_hot_t<8>());
-    std::vector<int32_t> spill_h;
-    for (int32_t i = 0; i < n; i++)
-        if (spill[(size_t)i]) spill_h.push_back(i);
+    // restricted pods (elig_class != 0) go on their own list (k_eval_elig answers every resource itself) and off
+    // the spill list
+    std::vector<int32_t> spill_h, elig_h;
+    int32_t n_spill_width = 0, max_elig = 0;
+    for (int32_t i = 0; i < n; i++) {
+        n_spill_width += spill[(size_t)i] ? 1 : 0;
+        if (rows[i].elig_class != 0) {
+            elig_h.push_back(i);
+            max_elig = std::max(max_elig, rows[i].elig_class < 0 ? INT32_MAX : rows[i].elig_class);
+        } else if (spill[(size_t)i]) {
+            spill_h.push_back(i);
+        }
+    }
+    // a restricted list on the device: ascending, then sorted by class (launch_elig); `cls_of(x)`: entry x's class
+    auto elig_orders = [&](const std::vector<int32_t> &asc, auto cls_of) {
+        std::vector<int32_t> both(asc);
+        std::vector<int32_t> by(asc);
+        std::stable_sort(by.begin(), by.end(), [&](int32_t x, int32_t y) { return cls_of(x) < cls_of(y); });
+        both.insert(both.end(), by.begin(), by.end());
+        return both;
+    };
     // (a device list grows on demand; a batch without spill pods allocates and copies nothing)
     auto upload_spill = [&](const std::vector<int32_t> &l, int32_t *&dst, size_t &cap) -> hipError_t {
         if (l.empty()) return hipSuccess;
@@ -4525,7 +4892,13 @@ kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     e->spill_h.clear();      // (set again below, once the list is on the device)
     e->eq_spill_h.clear();
+    e->elig_h.clear();
+    e->eq_elig_h.clear();
     HIP_TRY(e, upload_spill(spill_h, e->spill_list, e->spill_cap));
+    // (the uploads' sources live until the stream synchronisation at the end)
+    const std::vector<int32_t> elig_both = elig_orders(elig_h, [&](int32_t i) { return (uint32_t)rows[i].elig_class; });
+    std::vector<int32_t> eq_elig_both;
+    HIP_TRY(e, upload_spill(elig_both, e->elig_list, e->elig_cap));
     if (n > e->pods_cap || hot.size() > e->hot_bytes) {
         if (e->pods) HIP_TRY(e, hipFree(e->pods));
         if (e->hot) HIP_TRY(e, hipFree(e->hot));
@@ -4646,9 +5019,13 @@ kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
                 HIP_TRY(e, hipMalloc(&e->eq_hot, uh.size()));
                 HIP_TRY(e, h2d(e, e->eq_hot, uh.data(), uh.size(), e->stream));
             }
-            for (int32_t k = 0; k < u; k++)   // the distinct rows' spill list (reps ascend, so does it)
-                if (spill[(size_t)reps[(size_t)k]]) e->eq_spill_h.push_back(k);
+            for (int32_t k = 0; k < u; k++) {   // the distinct rows' spill and restricted lists (reps ascend, so do they)
+                if (udev[(size_t)k].elig != 0) e->eq_elig_h.push_back(k);
+                else if (spill[(size_t)reps[(size_t)k]]) e->eq_spill_h.push_back(k);
+            }
             HIP_TRY(e, upload_spill(e->eq_spill_h, e->eq_spill_list, e->eq_spill_cap));
+            eq_elig_both = elig_orders(e->eq_elig_h, [&](int32_t k) { return udev[(size_t)k].elig; });
+            HIP_TRY(e, upload_spill(eq_elig_both, e->eq_elig_list, e->eq_elig_cap));
             e->eq_perm_on = (e->cfg.enabled_plugins & KG_PLUGIN_NUMA) && u > 64;
             if (e->eq_perm_on) {
                 const std::vector<int32_t> order = numa_order(reps);
@@ -4660,6 +5037,9 @@ kg_status kg_pods_set(kg_engine *e, const kg_pod_row *rows, int32_t n) {
     }
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     e->spill_h = std::move(spill_h);
+    e->elig_h = std::move(elig_h);
+    e->n_spill_width = n_spill_width;
+    e->max_pod_elig = max_elig;
     e->nslot = nslot;
     for (int s = 0; s < 8; s++) e->slot_res[s] = slot_res[s];
     e->n_pods = n;
@@ -4684,6 +5064,7 @@ kg_status kg_eval(kg_engine *e, int64_t now_ns, const kg_eval_out *out) {
     kg_status st = check_engine(e);
     if (st) return st;
     st = bind_ready(e, false);
+    if (!st) st = elig_ready(e);
     if (st) return st;
     if (!out) return set_err(e, KG_ERR_INVALID_ARG, "null output");
     if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised");
@@ -5000,6 +5381,7 @@ kg_status kg_place_chunk_eval(kg_engine *e, int64_t now_ns, int32_t pod_begin, i
     kg_status st = check_engine(e);
     if (st) return st;
     st = bind_ready(e, true);
+    if (!st) st = elig_ready(e);
     if (st) return st;
     hipStream_t main_s = e->stream;
     if (e->eval_stream) e->stream = e->eval_stream;   // chunk_eval launches on e->stream
@@ -5074,6 +5456,7 @@ kg_status kg_place_chunk_resolve_prev(kg_engine *e, int64_t now_ns, int32_t pod_
     kg_status st = check_engine(e);
     if (st) return st;
     st = bind_ready(e, true);
+    if (!st) st = elig_ready(e);
     if (st) return st;
     if (n_prev < 0 || n_prev > KG_MAX_CHUNK || (n_prev > 0 && !prev_nodes_dev))
         return set_err(e, KG_ERR_RANGE, "bad previous-chunk node list");
@@ -5089,6 +5472,7 @@ kg_status kg_place_chunk_resolve(kg_engine *e, int64_t now_ns, int32_t pod_begin
     kg_status st = check_engine(e);
     if (st) return st;
     st = bind_ready(e, true);
+    if (!st) st = elig_ready(e);
     if (st) return st;
     st = eval_join(e, partial_dev);
     if (st) return st;
@@ -5493,6 +5877,7 @@ kg_status place_loop(kg_engine *e, int64_t now_ns, int32_t *out_node, int64_t *o
     const bool pipelined = !bind_mode && !rsv_args(e).rsv && !(e->forms & KG_FORM_PLACE_SEQUENTIAL) &&
                            ((e->forms & KG_FORM_PLACE_PIPELINE) || (e->consts.plugins & KG_PLUGIN_NUMA));
     if (!st) st = quota_ready(e);   // (before the pipeline: chunk_resolve checks it too, with an evaluation in flight)
+    if (!st) st = elig_ready(e);
     if (st) {
         if (sharded) (void)comm_agree(e, st);   // the peers' one agreement of this call (here or in place_pipelined)
         return st;
@@ -5827,6 +6212,9 @@ kg_status kg_cycle_one(kg_engine *e, const kg_pod_row *pod, int64_t now_ns, uint
     const uint32_t plug = e->cfg.enabled_plugins;
     const bool numa_on = (plug & KG_PLUGIN_NUMA) != 0;
     if (!kg_pod_row_in_bounds(*pod)) return set_err(e, KG_ERR_RANGE, "pod: request outside the engine bounds");
+    if (pod->elig_class < 0 || pod->elig_class > e->pl.elig_classes)
+        return set_err(e, KG_ERR_RANGE, "pod: elig_class %d outside the loaded eligibility classes (have %d: kg_elig_set)",
+                       pod->elig_class, e->pl.elig_classes);
     const bool numa_pod = numa_on && !(pod->flags & KG_POD_NUMA_SKIP);
     if (numa_pod && kg_numa_list_count(*pod) > KG_NUMA_MAX_LISTS)
         return set_err(e, KG_ERR_UNSUPPORTED, "pod: more than %d NUMA hint lists", KG_NUMA_MAX_LISTS);

@@ -909,6 +909,7 @@ void kg_pod_dev_from_row(const kg_config &c, const kg_pod_row &row, kg_pod_dev &
     d.rsv_owner = row.rsv_owner_class;
     d.rsv_aff = row.rsv_affinity_class;
     d.quota = (c.enabled_plugins & KG_PLUGIN_ELASTICQUOTA) ? row.quota : -1;
+    d.elig = (uint32_t)row.elig_class;
     if ((c.enabled_plugins & KG_PLUGIN_RESERVATION) && row.rsv_affinity_class >= 0) d.flags |= KGP_RSV_REQUIRED;
 }
 

@@ -175,14 +175,16 @@ def place_chunk_of(cfg: np.ndarray) -> int:
 
 
 def sharded_engine(cfg: np.ndarray, node_rows: np.ndarray, pod_rows: np.ndarray, device: torch.device,
-                   group=None, reservations: Optional[np.ndarray] = None, quotas: Optional[np.ndarray] = None):
+                   group=None, reservations: Optional[np.ndarray] = None, quotas: Optional[np.ndarray] = None,
+                   eligibility: Optional[np.ndarray] = None):
     """A HIP engine on `device` holding the full snapshot, restricted to this rank's node shard.
 
     The engine is bound to a dedicated torch stream (``eng.torch_stream``); `place_sharded` runs the
     collectives and tensor ops on that same stream, so engine kernels and merges are ordered. (The
     legacy null stream cannot be shared: ``kg_set_stream(NULL)`` means an engine-owned stream.)
     Reservation slots and ElasticQuota groups are replicated like the snapshot: every rank evaluates
-    all reservation nodes and applies the same quota gate in its (identical) resolve."""
+    all reservation nodes and applies the same quota gate in its (identical) resolve.  `eligibility` (the node
+    eligibility classes of Engine.set_eligibility, global node indices) is loaded whole on every rank too."""
     from .engine import Engine
 
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -200,6 +202,8 @@ def sharded_engine(cfg: np.ndarray, node_rows: np.ndarray, pod_rows: np.ndarray,
         eng.set_reservations(reservations)
     if quotas is not None:
         eng.set_quotas(quotas)
+    if eligibility is not None:
+        eng.set_eligibility(eligibility)
     eng.set_pods(pod_rows)
     begin, end = shard_range(len(node_rows), rank, world)
     eng.set_shard(begin, end)
@@ -209,7 +213,8 @@ def sharded_engine(cfg: np.ndarray, node_rows: np.ndarray, pod_rows: np.ndarray,
 def native_engine(cfg: np.ndarray, node_rows: np.ndarray, pod_rows: np.ndarray, device: torch.device, group=None,
                   reservations: Optional[np.ndarray] = None, quotas: Optional[np.ndarray] = None,
                   stream: Optional[torch.cuda.Stream] = None, comm: str = "rccl", rank: Optional[int] = None,
-                  world: Optional[int] = None, shm_name: Optional[str] = None):
+                  world: Optional[int] = None, shm_name: Optional[str] = None,
+                  eligibility: Optional[np.ndarray] = None):
     """A HIP engine holding the full snapshot, restricted to this rank's shard, with its own communicator: the
     engine then runs the whole sharded placement natively (Engine.place_sharded = kg_place_sharded), the chunk loop,
     the partial-key merges and the replicated resolve / host Reserve steps in C++.
@@ -217,7 +222,8 @@ def native_engine(cfg: np.ndarray, node_rows: np.ndarray, pod_rows: np.ndarray, 
     comm="rccl": an RCCL communicator over the group (kg_comm_init; rank 0's unique id is broadcast through
     torch.distributed).  comm="loopback": the host shared-memory communicator (kg_comm_init_loopback) — several ranks
     on ONE GPU (RCCL refuses two ranks on a device) run the same C++ loop; its segment name is rank 0's, broadcast
-    through torch.distributed, or `shm_name` when the caller starts the processes itself (rank / world given)."""
+    through torch.distributed, or `shm_name` when the caller starts the processes itself (rank / world given).
+    `eligibility`: the node eligibility classes (Engine.set_eligibility), the same table on every rank."""
     from .engine import Engine
 
     if rank is None:
@@ -234,6 +240,8 @@ def native_engine(cfg: np.ndarray, node_rows: np.ndarray, pod_rows: np.ndarray, 
         eng.set_reservations(reservations)
     if quotas is not None:
         eng.set_quotas(quotas)
+    if eligibility is not None:
+        eng.set_eligibility(eligibility)
     eng.set_pods(pod_rows)
     begin, end = shard_range(len(node_rows), rank, world)
     eng.set_shard(begin, end)
@@ -254,10 +262,11 @@ def native_engine(cfg: np.ndarray, node_rows: np.ndarray, pod_rows: np.ndarray, 
 
 def place(cfg: np.ndarray, node_rows: np.ndarray, pod_rows: np.ndarray, now_ns: int,
           device: Optional[torch.device] = None, group=None, reservations: Optional[np.ndarray] = None,
-          quotas: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """Convenience wrapper: build the sharded engine, place the batch, release the engine."""
+          quotas: Optional[np.ndarray] = None, eligibility: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Convenience wrapper: build the sharded engine, place the batch, release the engine.  `eligibility`: the
+    node eligibility classes the pod rows' elig_class names (Engine.set_eligibility), loaded on every rank."""
     device = device or torch.device("cuda", torch.cuda.current_device())
-    eng = sharded_engine(cfg, node_rows, pod_rows, device, group, reservations, quotas)
+    eng = sharded_engine(cfg, node_rows, pod_rows, device, group, reservations, quotas, eligibility)
     try:
         return place_sharded(eng, now_ns, device, chunk=place_chunk_of(cfg), group=group)
     finally:

@@ -208,6 +208,34 @@ class Engine:
         generic pair path."""
         return int(nat.lib().kg_pods_spill_count(self._h))
 
+    def restricted_count(self) -> int:
+        """kg_pods_restricted_count: pods of the uploaded batch with elig_class != 0."""
+        return int(nat.lib().kg_pods_restricted_count(self._h))
+
+    # node eligibility classes ---------------------------------------------------------------
+    def set_eligibility(self, masks) -> None:
+        """kg_elig_set: replace the eligibility table.  `masks`: bool [K][n_nodes] (True: the node is eligible for the
+        class), or the packed form uint64 [K][ceil(n_nodes / 64)] (bit n % 64 of word n // 64); None or K = 0 drops
+        the table.  A pod row with elig_class = k ≥ 1 may then only run on the nodes of class k − 1."""
+        words = (self.n_nodes + 63) // 64
+        if masks is None:
+            packed = np.zeros((0, words), dtype=np.uint64)
+        else:
+            masks = np.asarray(masks)
+            if masks.dtype == np.uint64:
+                packed = np.ascontiguousarray(masks).reshape(-1, words) if masks.size else np.zeros((0, words), np.uint64)
+            else:
+                packed = pack_eligibility(masks.reshape(-1, self.n_nodes) if masks.size else masks.reshape(0, self.n_nodes))
+        _check(nat.lib().kg_elig_set(self._h, nat.ptr(packed) if packed.size else None, len(packed), self.n_nodes), self,
+               "kg_elig_set")
+
+    def update_eligibility(self, cls: int, nodes, eligible) -> None:
+        """kg_elig_update: set (True) or clear (False) the bits of `nodes` in class `cls` (a node event)."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        el = np.ascontiguousarray(np.broadcast_to(np.asarray(eligible, dtype=bool), nodes.shape), dtype=np.uint8)
+        _check(nat.lib().kg_elig_update(self._h, int(cls), nat.ptr(nodes) if len(nodes) else None,
+                                        nat.ptr(el) if len(nodes) else None, len(nodes)), self, "kg_elig_update")
+
     # evaluation -------------------------------------------------------------------------
     @property
     def mask_words(self) -> int:
@@ -431,6 +459,16 @@ def decode_top1(keys: np.ndarray):
     node = np.where(ok, (np.uint64(0xFFFFFFFF) - (keys & np.uint64(0xFFFFFFFF))).astype(np.int64), -1)
     total = np.where(ok, (keys >> np.uint64(32)).astype(np.int64) - 1, -1)
     return node, total
+
+
+def pack_eligibility(masks: np.ndarray) -> np.ndarray:
+    """bool [K][n_nodes] → kg_elig_set's packed uint64 [K][ceil(n_nodes / 64)] (pad bits 0)."""
+    masks = np.asarray(masks, dtype=bool)
+    k, n = masks.shape
+    words = (n + 63) // 64
+    padded = np.zeros((k, words * 64), dtype=np.uint8)
+    padded[:, :n] = masks
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view(np.uint64).reshape(k, words)
 
 
 def unpack_mask(mask: np.ndarray, n_nodes: int) -> np.ndarray:
