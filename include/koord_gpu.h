@@ -843,6 +843,74 @@ typedef struct kg_cycle_out {
 kg_status kg_cycle_one(kg_engine *eng, const kg_pod_row *pod, int64_t now_ns, uint32_t flags,
                        const kg_eval_out *planes /* may be NULL */, kg_cycle_out *out);
 
+/* Rejection reasons: why a pod fits nowhere (upstream findNodesThatPassFilters' Diagnosis.NodeToStatusMap, the
+ * FailedScheduling event "0/N nodes are available: 312 Insufficient cpu, 97 Too many pods, ...", and the
+ * candidate nodes of preemption).  The reason word of a (pod, node) pair is a uint32 of KG_WHY_* bits, zero exactly
+ * when the pair is feasible (kg_eval's mask bit):
+ *   KG_WHY_ABSENT      the row is not KG_NODE_VALID (a removed node); no other bit is set then
+ *   KG_WHY_ELIG        the pod has elig_class = k >= 1 and the node's bit in class k - 1 is clear (kg_elig_set)
+ *   KG_WHY_FIT_PODS    NodeResourcesFit: pod_count + 1 > allowed_pods ("Too many pods")
+ *   KG_WHY_LOADAWARE   LoadAwareScheduling rejects the node for the pod's prod / non-prod variant (not a daemonset
+ *                      pod; NodeMetric expiry is judged at now_ns)
+ *   KG_WHY_NUMA        NodeNUMAResource: the pair is infeasible (not for a KG_POD_NUMA_SKIP pod)
+ *   KG_WHY_FIT_RES(r)  NodeResourcesFit, a pod with KG_POD_HAS_REQUEST: resource r is compared (r < 3, or bit r of
+ *                      request_present) and request[r] > alloc[r] - requested[r] ("Insufficient <r>").  Every
+ *                      failing resource is reported, not the first (upstream fitsRequest collects them all), and a
+ *                      zero cpu / memory / ephemeral-storage request fails where alloc - requested is negative.
+ * Every enabled plugin is evaluated on its own.  With KG_DIAG_FIRST_FAIL the word keeps only the bits of the first
+ * failing group in the reference's filter order - ABSENT, ELIG, NodeResourcesFit (all of its bits), LOADAWARE,
+ * NUMA: the default plugins, then config/manager/scheduler-config.yaml:65-70 - which is what NodeToStatusMap
+ * holds for the node; the NodeNUMAResource pair is then not evaluated where an earlier group failed.
+ * The pod-level word (KG_WHY_POD_*) holds the gates that do not depend on the node; the per-node words and
+ * counts do not include them (as the score planes):
+ *   KG_WHY_POD_QUOTA         ElasticQuota is enabled and the pod fails its PreFilter against the engine's quota
+ *                            state (kg_quota_set and the commits since; eq_check_parent_quota included)
+ *   KG_WHY_POD_RSV_REQUIRED  the pod requires a reservation and no reservation slots are loaded */
+#define KG_WHY_ABSENT 0x1u
+#define KG_WHY_ELIG 0x2u
+#define KG_WHY_FIT_PODS 0x4u
+#define KG_WHY_LOADAWARE 0x8u
+#define KG_WHY_NUMA 0x10u
+#define KG_WHY_FIT_RES_SHIFT 16
+#define KG_WHY_FIT_RES(r) (1u << (KG_WHY_FIT_RES_SHIFT + (r)))   /* r < KG_NUM_RES */
+#define KG_WHY_POD_QUOTA 0x1u
+#define KG_WHY_POD_RSV_REQUIRED 0x2u
+#define KG_DIAG_FIRST_FAIL 0x1u
+/* The reason word of one pair on host rows (no engine), as kg_row_eval: the single-node checks (preemption's
+ * SelectVictimsOnNode) without a device.  flags: 0 or KG_DIAG_FIRST_FAIL (others: KG_ERR_INVALID_ARG).  Like
+ * kg_row_eval it ignores kg_pod_row.elig_class (KG_WHY_ELIG is never set) and returns KG_ERR_UNSUPPORTED for a
+ * cpuset pair on a node whose valid CPU topology lacks CPU detail. */
+kg_status kg_row_why(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *pod, int64_t now_ns,
+                     uint32_t flags, uint32_t *why);
+
+/* The reasons of up to KG_DIAG_MAX_PODS pods against every node of the shard (kg_set_shard) in one call: one
+ * Diagnose per failed pod instead of one host call per node.  The pod rows travel with the call (as kg_cycle_one);
+ * the batch uploaded with kg_pods_set is neither read nor replaced.  The snapshot is read as it is now (after
+ * kg_place: the state after the batch's commits) and nothing is mutated: generation, rows and kg_counters.placed
+ * stay; eval_calls + 1, evals + n * (E - B), out_bytes / h2d_bytes as for the other entries.
+ *   counts  [n][KG_WHY_SLOTS] uint32 (required): counts[p][b], b = 0 and 1..27: the shard nodes whose word has bit b;
+ *           slot KG_WHY_SLOT_REJECTED: nodes with a non-zero word other than ABSENT; slot KG_WHY_SLOT_FEASIBLE:
+ *           nodes whose word is 0; the other slots 0.  Slots 0 + 30 + 31 sum to E - B.  Exact integers, identical
+ *           from run to run (no atomics: per-(pod, tile) partial counts, then a sum over the tiles).
+ *   pod_why [n] uint32 (may be NULL): the pod-level words
+ *   why     [n][64 * W] uint32 (may be NULL): the words, kg_eval's plane contract - W = ceil((E - B) / 64), column c
+ *           <=> node B + c, row stride 64 * W words, pad columns unspecified, nothing outside [n][64 * W] written,
+ *           a device pointer 16-byte aligned, no pre-zeroing needed.
+ * out_on_device != 0: the three pointers are device pointers on the engine's device.  The call returns after the
+ * launches completed either way.  An empty shard writes all-zero counts only.
+ * Errors (nothing launched): KG_ERR_RANGE for n > KG_DIAG_MAX_PODS, a row outside the engine bounds or an elig_class
+ * outside the loaded classes; KG_ERR_INVALID_ARG for unknown flags, n < 0 or a null counts / pods with n > 0;
+ * KG_ERR_STATE without a snapshot, on a stale engine, or for a quota index without a kg_quota_set group;
+ * KG_ERR_UNSUPPORTED when Reservation is enabled with slots loaded (the restore changes NodeInfo per pair), under
+ * NodeNUMAResource for a pod with KG_POD_NUMA_CPU_BIND or a snapshot holding a node with a CPU bind policy
+ * (kg_cycle_one's rule), and for a pod with more than two NUMA hint lists. */
+#define KG_WHY_SLOTS 32
+#define KG_WHY_SLOT_REJECTED 30   /* nodes with a non-zero word other than ABSENT */
+#define KG_WHY_SLOT_FEASIBLE 31   /* nodes whose word is 0 */
+#define KG_DIAG_MAX_PODS 256
+kg_status kg_diagnose(kg_engine *eng, const kg_pod_row *pods, int32_t n, int64_t now_ns, uint32_t flags,
+                      uint32_t *counts, uint32_t *pod_why, uint32_t *why, int32_t out_on_device);
+
 /* Measurement: when on, every k_eval launch (kg_eval, kg_place_chunk_eval) is bracketed by a
  * pair of HIP events on the engine stream (ring of 256).  kg_eval_kernel_times writes the
  * durations (ms) of the last min(n, recorded) launches, oldest first, and returns that count

@@ -51,6 +51,21 @@ NODE_CPU_BIND_NONE, NODE_CPU_BIND_FULL_PCPUS_ONLY, NODE_CPU_BIND_SPREAD_BY_PCPUS
 NUMA_ALLOC_DEFAULT, NUMA_ALLOC_MOST, NUMA_ALLOC_LEAST, NUMA_ALLOC_DISTRIBUTE_EVENLY = range(4)
 NOT_FOUND = 1   # KG_NOT_FOUND
 CYCLE_COMMIT = 0x1   # KG_CYCLE_COMMIT: kg_cycle_one reserves the chosen node in the same launch
+# rejection reasons (kg_row_why / kg_diagnose): the per-pair word, the pod-level word, the flag, the count slots
+WHY_ABSENT, WHY_ELIG, WHY_FIT_PODS, WHY_LOADAWARE, WHY_NUMA = 0x1, 0x2, 0x4, 0x8, 0x10
+WHY_FIT_RES_SHIFT = 16
+
+
+def WHY_FIT_RES(r: int) -> int:
+    """KG_WHY_FIT_RES(r): NodeResourcesFit rejects on resource r ("Insufficient <r>")."""
+    return 1 << (WHY_FIT_RES_SHIFT + r)
+
+
+WHY_FIT_MASK = WHY_FIT_PODS | (((1 << 12) - 1) << WHY_FIT_RES_SHIFT)   # every NodeResourcesFit bit
+WHY_POD_QUOTA, WHY_POD_RSV_REQUIRED = 0x1, 0x2
+DIAG_FIRST_FAIL = 0x1
+WHY_SLOTS, WHY_SLOT_REJECTED, WHY_SLOT_FEASIBLE = 32, 30, 31
+DIAG_MAX_PODS = 256
 NODE_VALID, NODE_HAS_METRIC, NODE_HAS_UPDATE_TIME, NODE_LA_PASS_NONPROD, NODE_LA_PASS_PROD = 0x1, 0x2, 0x4, 0x8, 0x10
 NODE_NUMA_OPTIONS, NODE_NUMA_TOPO_VALID, NODE_NUMA_TOPO_INVALID = 0x40, 0x80, 0x100
 
@@ -235,7 +250,7 @@ EXPORTED = [
     "kg_place_chunk_resolve_prev", "kg_set_eval_stream", "kg_set_forms", "kg_comm_unique_id", "kg_comm_init",
     "kg_place_sharded", "kg_counters_get", "kg_counters_reset", "kg_comm_init_loopback", "kg_comm_kind",
     "kg_cycle_one", "kg_batch_slot_map", "kg_pods_spill_count", "kg_elig_set", "kg_elig_update",
-    "kg_pods_restricted_count",
+    "kg_pods_restricted_count", "kg_row_why", "kg_diagnose",
 ]
 
 _lib = None
@@ -290,6 +305,8 @@ def lib() -> ctypes.CDLL:
         "kg_batch_slot_map": (i32, [vp, vp, i32, vp, vp, vp]), "kg_pods_spill_count": (i32, [vp]),
         "kg_elig_set": (i32, [vp, vp, i32, i32]), "kg_elig_update": (i32, [vp, i32, vp, vp, i32]),
         "kg_pods_restricted_count": (i32, [vp]),
+        "kg_row_why": (i32, [vp, vp, vp, i64, ctypes.c_uint32, vp]),
+        "kg_diagnose": (i32, [vp, vp, i32, i64, ctypes.c_uint32, vp, vp, vp, i32]),
     }
     for name, (res, args) in sig.items():
         if host_only and not hasattr(L, name):

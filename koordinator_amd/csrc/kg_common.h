@@ -1701,3 +1701,75 @@ KG_HD void kg_quota_commit(kg_quota *qs, int32_t g, const kg_pod_dev &p) {
         if (p.flags & KG_POD_NON_PREEMPTIBLE) kg_rl_add_pod(qs[a].non_preemptible_used, p);
     }
 }
+
+// ---- rejection reasons (kg_row_why, kg_diagnose) --------------------------------------------
+// The reason word of one (pod, node) pair (KG_WHY_*): every enabled Filter plugin evaluated on its own, zero
+// exactly when the pair is feasible.  NodeResourcesFit reports every failing resource (upstream fitsRequest
+// collects all InsufficientResource entries), a zero native request included where Allocatable − Requested is
+// negative.  The parts are shared by the canonical-row form below and k_why's register form, so both build the
+// same word.
+#define KG_WHY_FIT_MASK (KG_WHY_FIT_PODS | (((1u << KG_NUM_RES) - 1u) << KG_WHY_FIT_RES_SHIFT))
+
+// KG_DIAG_FIRST_FAIL: the bits of the first failing group in the reference's filter order (what NodeToStatusMap
+// holds for the node): ABSENT, ELIG, NodeResourcesFit (all of its bits), LOADAWARE, NUMA
+KG_HD uint32_t kg_why_first(uint32_t w) {
+    if (w & KG_WHY_ABSENT) return KG_WHY_ABSENT;
+    if (w & KG_WHY_ELIG) return KG_WHY_ELIG;
+    if (w & KG_WHY_FIT_MASK) return w & KG_WHY_FIT_MASK;
+    if (w & KG_WHY_LOADAWARE) return KG_WHY_LOADAWARE;
+    return w & KG_WHY_NUMA;
+}
+
+// resource r of the Fit filter: compared (a native, or a requested scalar key) and above the node's free amount
+KG_HD uint32_t kg_why_fit_res(const kg_pod_dev &p, int r, int64_t free_r) {
+    const bool chk = r < 3 || ((p.request_present >> r) & 1u);
+    return (chk && p.req[r] > free_r) ? KG_WHY_FIT_RES(r) : 0u;
+}
+
+// LoadAware's bit from the derived flags and the NodeMetric expiry at `now`
+KG_HD uint32_t kg_why_la(const kg_consts &c, uint32_t df, bool expired, const kg_pod_dev &p) {
+    if (!(c.plugins & KG_PLUGIN_LOADAWARE) || (p.flags & KG_POD_DAEMONSET)) return 0u;
+    return kg_la_pass(c, df, expired, (p.flags & KG_POD_PROD) ? 1 : 0) ? 0u : KG_WHY_LOADAWARE;
+}
+
+// the NodeNUMAResource bit and the first-fail reduction on top of the other groups' bits `w` (not ABSENT): under
+// KG_DIAG_FIRST_FAIL the pair is not evaluated where an earlier group failed
+template <bool NUMA>
+KG_HD uint32_t kg_why_finish(const kg_consts &c, const kg_node_row &row, const kg_pod_dev &p, uint32_t w, uint32_t flags) {
+    const bool first = (flags & KG_DIAG_FIRST_FAIL) != 0;
+    if constexpr (NUMA) {
+        if ((c.plugins & KG_PLUGIN_NUMA) && !(p.flags & KG_POD_NUMA_SKIP) && !(first && w != 0u)) {
+            if (!(kg_numa_eval_any(c, row, p) >> 32)) w |= KG_WHY_NUMA;
+        }
+    }
+    return first ? kg_why_first(w) : w;
+}
+
+// The word from the canonical row (the host entry; on the device the nodes outside the fp64 bounds and the pods
+// that compare a later named slot, as kg_pair_view).  `elig_ok`: the pod's eligibility class on the node.
+template <bool NUMA = true>
+KG_HD uint32_t kg_pair_why(const kg_consts &c, const kg_node_row &row, uint32_t df, const kg_pod_dev &p, int64_t now_ns,
+                           uint32_t flags, bool elig_ok = true) {
+    if (!(row.flags & KG_NODE_VALID)) return KG_WHY_ABSENT;
+    uint32_t w = elig_ok ? 0u : KG_WHY_ELIG;
+    if (c.plugins & KG_PLUGIN_FIT) {
+        if ((int64_t)row.pod_count + 1 > (int64_t)row.allowed_pods) w |= KG_WHY_FIT_PODS;
+        if (p.flags & KG_POD_HAS_REQUEST) {
+#pragma unroll
+            for (int r = 0; r < KG_NUM_RES; r++) w |= kg_why_fit_res(p, r, row.alloc[r] - row.requested[r]);
+        }
+    }
+    w |= kg_why_la(c, df, kg_metric_expired(c, df, row.metric_update_ns, now_ns), p);
+    return kg_why_finish<NUMA>(c, row, p, w, flags);
+}
+
+// The pod-level word (KG_WHY_POD_*): the gates that do not depend on the node
+KG_HD uint32_t kg_pod_why(const kg_consts &c, const kg_quota *qs, int32_t n_quota, int32_t check_parent, bool rsv_slots,
+                          const kg_pod_dev &p) {
+    uint32_t w = 0;
+    if ((c.plugins & KG_PLUGIN_ELASTICQUOTA) && qs && p.quota >= 0 && p.quota < n_quota &&
+        !kg_quota_pass(qs, p.quota, p, check_parent != 0))
+        w |= KG_WHY_POD_QUOTA;
+    if ((p.flags & KGP_RSV_REQUIRED) && !rsv_slots) w |= KG_WHY_POD_RSV_REQUIRED;
+    return w;
+}

@@ -81,6 +81,8 @@
 //   101-105 k_eval_spill              listed pod (read), score pairs, mask words, tile keys, top-k tile keys
 //   106-112 k_eval_elig               listed pod (read), eligibility words (read), tile count (read), score pairs,
 //                                     mask words, tile keys, top-k tile keys
+//   113-115 k_why                     pod row (read), reason plane, per-(pod, tile) partial counts
+//   116-118 k_why_reduce              partial counts (read), counts, pod-level words
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -3356,6 +3358,163 @@ __global__ __launch_bounds__(256) void k_cycle_one(kg_consts c, kg_planes pl, kg
 }
 
 // ---------------------------------------------------------------------------------------
+// kg_diagnose: the reason words of listed pods over the shard (k_why) and their per-reason node counts
+// ---------------------------------------------------------------------------------------
+struct WhyArgs {
+    int64_t node_end;            // the shard's end
+    int64_t col_begin;           // its begin: column c of a plane row ⇔ node col_begin + c
+    int64_t stride;              // words per plane row: 64 · W
+    int64_t now_ns;
+    int32_t tile_begin, shard_tiles;
+    int32_t n_groups, pods_per_group;
+    int32_t n_pods;
+    uint32_t flags;              // KG_DIAG_*
+};
+
+// OR over the 64 lanes, returned wave-uniform (wave_max_u32's DPP ladder: 0 is the identity of OR too)
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// The reason word of one pair.  A node inside the fp64 bounds and a pod within the fast resources compare against
+// the node registers (the free_ planes and dflags eval_fast reads); a KGD_SLOW node or a pod that compares a later
+// named slot takes the canonical row (kg_pair_why), as eval_pair_plugins sends those pairs to kg_pair_exact.
+template <bool NUMA>
+__device__ __forceinline__ uint32_t why_pair(const kg_consts &c, const kg_planes &pl, const kg_pod_dev &p,
+                                             const NodeRegs &n, bool expired, int64_t node, int64_t now_ns,
+                                             uint32_t flags) {
+    const bool el = kg_elig_ok(pl, p, node);
+    if ((n.df & KGD_SLOW) || (p.cmp_mask >> KG_FAST_RES)) return kg_pair_why<NUMA>(c, pl.rows[node], n.df, p, now_ns, flags, el);
+    if (!(n.df & KGD_VALID)) return KG_WHY_ABSENT;
+    uint32_t w = el ? 0u : KG_WHY_ELIG;
+    if (c.plugins & KG_PLUGIN_FIT) {
+        if (n.df & KGD_PODS_FULL) w |= KG_WHY_FIT_PODS;
+        // (both masks are empty for a pod without KG_POD_HAS_REQUEST)
+#pragma unroll
+        for (int r = 0; r < KG_FAST_RES; r++)
+            if (((p.cmp_mask >> r) & 1u) && p.req[r] > n.free_[r]) w |= KG_WHY_FIT_RES(r);
+        if ((p.zero_native_mask & 1u) && (n.df & KGD_OVER_CPU)) w |= KG_WHY_FIT_RES(KG_RES_CPU);
+        if ((p.zero_native_mask & 2u) && (n.df & KGD_OVER_MEM)) w |= KG_WHY_FIT_RES(KG_RES_MEMORY);
+        if ((p.zero_native_mask & 4u) && (n.df & KGD_OVER_EPH)) w |= KG_WHY_FIT_RES(KG_RES_EPHEMERAL_STORAGE);
+    }
+    w |= kg_why_la(c, n.df, expired, p);
+    return kg_why_finish<NUMA>(c, pl.rows[node], p, w, flags);
+}
+
+// k_eval_spill's geometry: one workgroup = one 1024-node tile × a group of the pods (XCD-aware order: the groups
+// of one tile are consecutive workgroups of one XCD), two nodes per lane, the tile's node registers loaded once,
+// pod rows staged KG_SPILL_CHUNK at a time in LDS (NUMA: the out-of-line NodeNUMAResource code takes the row by
+// address).  PLANE: the words go to `why` [n][stride] as coalesced 32-bit stores, a 64-node segment only inside
+// the padded row.  Counting: per pod, each wave ORs its words to the wave-uniform set of live bits and takes one
+// ballot + popcount per live bit (and for the rejected / feasible slots); the workgroup's eight waves are summed
+// through LDS and the (pod, tile) partial counts are stored into `slab` [n][shard_tiles][KG_WHY_SLOTS] with plain
+// stores, every slot of it: no atomics, so the sums do not depend on any order.
+template <bool NUMA, bool PLANE>
+__global__ __launch_bounds__(KG_BLOCK) void k_why(kg_consts c, kg_planes pl, WhyArgs a,
+                                                  const kg_pod_dev *__restrict__ pods, uint32_t *__restrict__ why,
+                                                  uint32_t *__restrict__ slab) {
+    __shared__ __attribute__((aligned(16))) kg_pod_dev lp[KG_SPILL_CHUNK];
+    __shared__ uint32_t lcnt[KG_SPILL_CHUNK][KG_BLOCK / 64][KG_WHY_SLOTS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x, xcd = b % KG_XCDS, r = b / KG_XCDS;
+    const int tile_rel = (r / a.n_groups) * KG_XCDS + xcd, group = r % a.n_groups;
+    if (tile_rel >= a.shard_tiles) return;   // grid padded to a multiple of 8 tiles; block-uniform
+    const int tile = a.tile_begin + tile_rel;
+    const int64_t wave_base = (int64_t)tile * KG_TILE + wave * 128;
+    const int64_t node0 = wave_base + lane, node1 = node0 + 64;
+    const bool in0 = node0 < a.node_end, in1 = node1 < a.node_end;
+    const BatchMasks bm{(1u << KG_FAST_RES) - 1u, 0u};   // every fast resource's free_ plane, no score plane
+    NodeRegs n0, n1;
+    load_node(c, pl, node0, in0, bm, a.now_ns, n0);
+    load_node(c, pl, node1, in1, bm, a.now_ns, n1);
+    const bool la_on = (c.plugins & KG_PLUGIN_LOADAWARE) != 0;
+    const bool exp0 = la_on && kg_metric_expired(c, n0.df, in0 ? pl.metric_ns[node0] : 0, a.now_ns);
+    const bool exp1 = la_on && kg_metric_expired(c, n1.df, in1 ? pl.metric_ns[node1] : 0, a.now_ns);
+    // output columns: a 64-node segment is written iff it lies inside the padded row (wave-uniform)
+    const int64_t col0 = wave_base - a.col_begin;
+    [[maybe_unused]] const bool seg0 = col0 < a.stride, seg1 = col0 + 64 < a.stride;
+    constexpr int POD_DW = (int)(sizeof(kg_pod_dev) / 4);
+    const int gb = group * a.pods_per_group;
+    const int ge = min(gb + a.pods_per_group, a.n_pods);
+    for (int q0 = gb; q0 < ge; q0 += KG_SPILL_CHUNK) {
+        const int nq = min(KG_SPILL_CHUNK, ge - q0);
+        for (int k = tid; k < nq * POD_DW; k += KG_BLOCK) {
+            const int j = k / POD_DW, w = k - j * POD_DW;
+            reinterpret_cast<uint32_t *>(&lp[j])[w] =
+                KG_IN(113, q0 + j, a.n_pods) ? reinterpret_cast<const uint32_t *>(pods + q0 + j)[w] : 0u;
+        }
+        __syncthreads();
+        for (int j = 0; j < nq; j++) {
+            const int p = q0 + j;
+            uint32_t w0 = 0u, w1 = 0u;
+            if (in0) w0 = why_pair<NUMA>(c, pl, lp[j], n0, exp0, node0, a.now_ns, a.flags);
+            if (in1) w1 = why_pair<NUMA>(c, pl, lp[j], n1, exp1, node1, a.now_ns, a.flags);
+            if constexpr (PLANE) {
+                uint32_t *d = why + (int64_t)p * a.stride + col0 + lane;
+                if (seg0 && KG_IN2(114, p, a.n_pods, col0 + lane, a.stride)) d[0] = w0;
+                if (seg1 && KG_IN2(114, p, a.n_pods, col0 + 64 + lane, a.stride)) d[64] = w1;
+            }
+            // lane s ends up holding the wave's count of slot s
+            uint32_t mine = 0u;
+            uint32_t live = wave_or_u32(w0 | w1);
+            while (live) {   // (wave-uniform: a scalar loop)
+                const int s = __builtin_ctz(live);
+                live &= live - 1u;
+                const uint32_t cnt = (uint32_t)__popcll(__ballot((w0 >> s) & 1u)) + (uint32_t)__popcll(__ballot((w1 >> s) & 1u));
+                if (lane == s) mine = cnt;
+            }
+            const uint32_t rej = (uint32_t)__popcll(__ballot(w0 != 0u && w0 != KG_WHY_ABSENT)) +
+                                 (uint32_t)__popcll(__ballot(w1 != 0u && w1 != KG_WHY_ABSENT));
+            const uint32_t feas = (uint32_t)__popcll(__ballot(in0 && w0 == 0u)) + (uint32_t)__popcll(__ballot(in1 && w1 == 0u));
+            if (lane == KG_WHY_SLOT_REJECTED) mine = rej;
+            if (lane == KG_WHY_SLOT_FEASIBLE) mine = feas;
+            if (lane < KG_WHY_SLOTS) lcnt[j][wave][lane] = mine;
+        }
+        __syncthreads();
+        for (int j = wave; j < nq; j += KG_BLOCK / 64) {   // a wave per pod
+            const int p = q0 + j;
+            if (lane < KG_WHY_SLOTS) {
+                uint32_t s = 0u;
+#pragma unroll
+                for (int i = 0; i < KG_BLOCK / 64; i++) s += lcnt[j][i][lane];
+                if (KG_IN2(115, p, a.n_pods, tile_rel, a.shard_tiles))
+                    slab[((int64_t)p * a.shard_tiles + tile_rel) * KG_WHY_SLOTS + lane] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Sum of the tiles' partial counts: a wave per (pod, half of the slots), lane = tile phase · 16 + slot, so a tile's
+// 16 slots are one 64-byte read; every slot of every pod is written (the caller zeroes nothing).  The wave of a
+// pod's first half also writes its pod-level word (kg_pod_why against the device quota state).
+__global__ __launch_bounds__(64) void k_why_reduce(kg_consts c, const uint32_t *__restrict__ slab, int32_t n_pods,
+                                                   int32_t tiles, const kg_pod_dev *__restrict__ pods,
+                                                   const kg_quota *__restrict__ quota, int32_t n_quota,
+                                                   int32_t check_parent, int32_t rsv_slots,
+                                                   uint32_t *__restrict__ counts, uint32_t *__restrict__ pod_why) {
+    const int p = blockIdx.x >> 1, h = blockIdx.x & 1;
+    if (p >= n_pods) return;   // block-uniform
+    const int lane = threadIdx.x, s = lane & 15, ph = lane >> 4;
+    uint32_t v = 0u;
+    for (int t = ph; t < tiles; t += 4)
+        if (KG_IN2(116, p, n_pods, t, tiles)) v += slab[((int64_t)p * tiles + t) * KG_WHY_SLOTS + h * 16 + s];
+    v += __shfl_down(v, 32, 64);
+    v += __shfl_down(v, 16, 64);
+    if (lane < 16 && KG_IN(117, p, n_pods)) counts[(int64_t)p * KG_WHY_SLOTS + h * 16 + lane] = v;
+    if (pod_why && h == 0 && lane == 0 && KG_IN(118, p, n_pods))
+        pod_why[p] = kg_pod_why(c, quota, n_quota, check_parent, rsv_slots != 0, pods[p]);
+}
+
+// ---------------------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------------------
 struct kg_engine {
@@ -3505,6 +3664,11 @@ struct kg_engine {
     // result in pinned host memory; allocated at the first call
     unsigned long long *cyc_words = nullptr;
     kg_cycle_out *cyc_out = nullptr;
+    // kg_diagnose: the call's pod rows, counts, pod-level words and per-(pod, tile) partial counts on the device
+    // (one buffer, grown on demand) and the pinned host block its pod rows and small outputs pass through
+    void *diag_mem = nullptr;
+    size_t diag_bytes = 0;
+    void *diag_host = nullptr;
     int32_t comm_rank = 0, comm_world = 0;
     hipStream_t eval_stream = nullptr;  // kg_set_eval_stream (kg_place_chunk_eval), nullptr ⇒ stream
     // recorded on eval_stream after each kg_place_chunk_eval, one per partial buffer (keyed by its address): a chunk
@@ -4527,6 +4691,8 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->comm_word) (void)hipFree(e->comm_word);
     if (e->cyc_words) (void)hipFree(e->cyc_words);
     if (e->cyc_out) (void)hipHostFree(e->cyc_out);
+    if (e->diag_mem) (void)hipFree(e->diag_mem);
+    if (e->diag_host) (void)hipHostFree(e->diag_host);
     if (e->hot_lax) (void)hipFree(e->hot_lax);
     if (e->eq_pods) (void)hipFree(e->eq_pods);
     if (e->eq_perm) (void)hipFree(e->eq_perm);
@@ -6302,6 +6468,124 @@ kg_status kg_cycle_one(kg_engine *e, const kg_pod_row *pod, int64_t now_ns, uint
         e->generation++;
         e->ctr.placed++;
     }
+    return bounds_verdict(e);
+}
+
+// The reasons of n pods over the shard: k_why (the words, the optional plane, per-(pod, tile) partial counts) and
+// k_why_reduce (their sums and the pod-level words), then one stream synchronisation.  Like kg_cycle_one the pod
+// rows travel with the call; the uploaded batch, the snapshot and the generation are not touched.
+kg_status kg_diagnose(kg_engine *e, const kg_pod_row *pods, int32_t n, int64_t now_ns, uint32_t flags, uint32_t *counts,
+                      uint32_t *pod_why, uint32_t *why, int32_t out_on_device) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (flags & ~KG_DIAG_FIRST_FAIL) return set_err(e, KG_ERR_INVALID_ARG, "unknown kg_diagnose flags 0x%x", flags);
+    if (n < 0 || (n > 0 && (!pods || !counts))) return set_err(e, KG_ERR_INVALID_ARG, "null pods or counts");
+    if (n > KG_DIAG_MAX_PODS) return set_err(e, KG_ERR_RANGE, "kg_diagnose takes at most %d pods (got %d)", KG_DIAG_MAX_PODS, n);
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised");
+    const uint32_t plug = e->cfg.enabled_plugins;
+    const bool numa_on = (plug & KG_PLUGIN_NUMA) != 0;
+    for (int32_t i = 0; i < n; i++) {
+        const kg_pod_row &pod = pods[i];
+        if (!kg_pod_row_in_bounds(pod)) return set_err(e, KG_ERR_RANGE, "pod %d: request outside the engine bounds", i);
+        if (pod.elig_class < 0 || pod.elig_class > e->pl.elig_classes)
+            return set_err(e, KG_ERR_RANGE, "pod %d: elig_class %d outside the loaded eligibility classes (have %d: kg_elig_set)",
+                           i, pod.elig_class, e->pl.elig_classes);
+    }
+    // what the per-pair word does not answer
+    if ((plug & KG_PLUGIN_RESERVATION) && e->n_rn > 0)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_diagnose with reservation slots loaded (the restore changes NodeInfo per pair)");
+    if (numa_on && e->n_node_bind_nodes > 0)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_diagnose does not answer cpuset binding (a node with a CPU bind policy)");
+    for (int32_t i = 0; i < n; i++) {
+        const kg_pod_row &pod = pods[i];
+        const bool numa_pod = numa_on && !(pod.flags & KG_POD_NUMA_SKIP);
+        if (numa_pod && (pod.flags & KG_POD_NUMA_CPU_BIND))
+            return set_err(e, KG_ERR_UNSUPPORTED, "pod %d: kg_diagnose does not answer cpuset binding", i);
+        if (numa_pod && kg_numa_list_count(pod) > KG_NUMA_MAX_LISTS)
+            return set_err(e, KG_ERR_UNSUPPORTED, "pod %d: more than %d NUMA hint lists", i, KG_NUMA_MAX_LISTS);
+        if ((plug & KG_PLUGIN_ELASTICQUOTA) && pod.quota >= e->n_quota)
+            return set_err(e, KG_ERR_STATE, "pod %d: quota index %d without a kg_quota_set group (have %d)", i, pod.quota,
+                           e->n_quota);
+    }
+    const bool dev = out_on_device != 0;
+    const int64_t width = e->shard_end - e->shard_begin;
+    const int64_t words = (width + 63) / 64, stride = words * 64;
+    const size_t cnt_b = (size_t)n * KG_WHY_SLOTS * 4, pw_b = (size_t)n * 4, why_b = (size_t)n * (size_t)stride * 4;
+    e->ctr.eval_calls++;
+    e->ctr.evals += (uint64_t)n * (uint64_t)(width > 0 ? width : 0);
+    e->ctr.out_bytes += cnt_b + (pod_why ? pw_b : 0) + (why ? why_b : 0);
+    if (n == 0) return KG_OK;
+    if (width <= 0) {   // an empty shard: all-zero counts, nothing to launch
+        if (dev) {
+            HIP_TRY(e, hipMemsetAsync(counts, 0, cnt_b, e->stream));
+            HIP_TRY(e, hipStreamSynchronize(e->stream));
+        } else {
+            memset(counts, 0, cnt_b);
+        }
+        return KG_OK;
+    }
+    const int64_t tile_begin = e->shard_begin / KG_TILE;
+    const int64_t shard_tiles = (e->shard_end + KG_TILE - 1) / KG_TILE - tile_begin;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t pods_b = sizeof(kg_pod_dev) * (size_t)n;
+    const size_t slab_b = (size_t)n * (size_t)shard_tiles * KG_WHY_SLOTS * 4;
+    const size_t need = up(pods_b) + up(cnt_b) + up(pw_b) + up(slab_b);
+    if (e->diag_bytes < need) {
+        if (e->diag_mem) HIP_TRY(e, hipFree(e->diag_mem));
+        e->diag_mem = nullptr;
+        e->diag_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->diag_mem, need));
+        e->diag_bytes = need;
+    }
+    if (!e->diag_host) HIP_TRY(e, hipHostMalloc(&e->diag_host, sizeof(kg_pod_dev) * KG_DIAG_MAX_PODS, hipHostMallocDefault));
+    char *m = (char *)e->diag_mem;
+    kg_pod_dev *pods_d = (kg_pod_dev *)m;
+    uint32_t *cnt_d = dev ? counts : (uint32_t *)(m + up(pods_b));
+    uint32_t *pw_d = !pod_why ? nullptr : dev ? pod_why : (uint32_t *)(m + up(pods_b) + up(cnt_b));
+    uint32_t *slab = (uint32_t *)(m + up(pods_b) + up(cnt_b) + up(pw_b));
+    uint32_t *why_d = nullptr;
+    if (why && dev) {
+        why_d = why;
+    } else if (why) {   // a host plane: staged in scratch, copied back ahead of the synchronisation
+        st = ensure_scratch(e, why_b + 256);
+        if (st) return st;
+        why_d = (uint32_t *)e->scratch;
+    }
+    kg_pod_dev *pods_h = (kg_pod_dev *)e->diag_host;
+    for (int32_t i = 0; i < n; i++) kg_pod_dev_from_row(e->cfg, pods[i], pods_h[i]);
+    HIP_TRY(e, h2d(e, pods_d, pods_h, pods_b, e->stream));
+    WhyArgs a{};
+    a.node_end = e->shard_end;
+    a.col_begin = e->shard_begin;
+    a.stride = stride;
+    a.now_ns = now_ns;
+    a.tile_begin = (int32_t)tile_begin;
+    a.shard_tiles = (int32_t)shard_tiles;
+    // pods per workgroup as launch_spill: whole LDS passes, about 2048 workgroups on a large launch
+    int64_t ppg = ((int64_t)n * shard_tiles + 2047) / 2048;
+    ppg = (ppg + KG_SPILL_CHUNK - 1) / KG_SPILL_CHUNK * KG_SPILL_CHUNK;
+    if (ppg < KG_SPILL_CHUNK) ppg = KG_SPILL_CHUNK;
+    const int64_t groups = (n + ppg - 1) / ppg;
+    const int64_t blocks = (shard_tiles + KG_XCDS - 1) / KG_XCDS * KG_XCDS * groups;
+    a.n_groups = (int32_t)groups;
+    a.pods_per_group = (int32_t)ppg;
+    a.n_pods = n;
+    a.flags = flags;
+    auto *kern = numa_on ? (why_d ? k_why<true, true> : k_why<true, false>) : (why_d ? k_why<false, true> : k_why<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(KG_BLOCK), 0, e->stream, e->consts, e->pl, a,
+                       (const kg_pod_dev *)pods_d, why_d, slab);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(k_why_reduce, dim3((unsigned)(2 * n)), dim3(64), 0, e->stream, e->consts, (const uint32_t *)slab, n,
+                       (int32_t)shard_tiles, (const kg_pod_dev *)pods_d,
+                       (plug & KG_PLUGIN_ELASTICQUOTA) ? (const kg_quota *)e->quota : (const kg_quota *)nullptr, e->n_quota,
+                       (int32_t)(e->cfg.eq_check_parent_quota != 0), (int32_t)(e->n_rn > 0), cnt_d, pw_d);
+    HIP_TRY(e, hipGetLastError());
+    if (!dev) {
+        HIP_TRY(e, hipMemcpyAsync(counts, cnt_d, cnt_b, hipMemcpyDeviceToHost, e->stream));
+        if (pod_why) HIP_TRY(e, hipMemcpyAsync(pod_why, pw_d, pw_b, hipMemcpyDeviceToHost, e->stream));
+        if (why) HIP_TRY(e, hipMemcpyAsync(why, why_d, why_b, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the pinned pod rows are free for the next call)
     return bounds_verdict(e);
 }
 

@@ -783,6 +783,29 @@ kg_status kg_row_eval(const kg_config *cfg, const kg_node_row *node, const kg_po
     return KG_OK;
 }
 
+// The reason word of one pair through kg_pair_why, the function k_why runs for the nodes it takes from the
+// canonical row; like kg_row_eval no engine, no eligibility class and no reservation slots.
+kg_status kg_row_why(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *pod, int64_t now_ns,
+                     uint32_t flags, uint32_t *why) {
+    if (!cfg || !node || !pod || !why || (flags & ~KG_DIAG_FIRST_FAIL)) return KG_ERR_INVALID_ARG;
+    bool answered;
+    if (row_binds(*cfg, *node, *pod, answered) && !answered) return KG_ERR_UNSUPPORTED;
+    kg_consts k;
+    kg_consts_from_config(*cfg, k);
+    k.numa_bz = 1;   // a cpuset pair on a NUMA-policy node is answered here (kg_row_eval's kg_numa_pair_z)
+    kg_pod_dev pd;
+    kg_pod_dev_from_row(*cfg, *pod, pd);
+    // one-node planes, only for the derived flags
+    kg_node_row row = *node;
+    int64_t free_[KG_NUM_RES], metric_ns;
+    double fit_R[KG_NUM_RES], fit_F[KG_NUM_RES], la_R[2], la_F[4];
+    uint32_t dflags, fmask;
+    kg_planes pl{&row, free_, fit_R, fit_F, la_R, la_F, &metric_ns, &dflags, &fmask, 1};
+    kg_finalize_node(k, pl, 0);
+    *why = kg_pair_why<true>(k, row, dflags, pd, now_ns, flags);
+    return KG_OK;
+}
+
 kg_status kg_row_eval_rsv(const kg_config *cfg, const kg_node_row *node, const kg_reservation *rsv, int32_t n_rsv,
                           const kg_pod_row *pod, int64_t now_ns, int32_t *feasible, int32_t *fit_score,
                           int32_t *la_score, int32_t *numa_score, int32_t *rsv_raw, int64_t *order,

@@ -67,9 +67,12 @@ def plane_scores(cfg: Mapping, res: Mapping[str, np.ndarray], pod: int, n_nodes:
 
 
 def dump_eval(cfg: Mapping, res: Mapping[str, np.ndarray], n_nodes: int, top_n: int,
-              pod_refs: Optional[Sequence[str]] = None, node_names: Optional[Sequence[str]] = None) -> list:
+              pod_refs: Optional[Sequence[str]] = None, node_names: Optional[Sequence[str]] = None,
+              reasons=None) -> list:
     """One table per pod of a matrix-mode result (needs its mask and score planes); each is logged at
-    INFO like ``klog.Infof`` in debug.go:107 and returned."""
+    INFO like ``klog.Infof`` in debug.go:107 and returned.  ``reasons(p)`` (optional) gives the reason histogram of
+    pod ``p`` ("312 Insufficient cpu, 97 Too many pods", from ``Engine.diagnose``); it is asked for the pods
+    without a feasible node and logged like the FailedScheduling event ("0/N nodes are available: ...")."""
     tables = []
     if top_n <= 0 or "mask" not in res or "scores" not in res:
         return tables
@@ -80,5 +83,9 @@ def dump_eval(cfg: Mapping, res: Mapping[str, np.ndarray], n_nodes: int, top_n: 
         t = render_scores(top_n, ref, scores, names)
         log.info("Top%d scores for Pod: %s, feasibleNodes: %d, plugins:%s\n%s", top_n, ref, len(nodes),
                  sorted(scores), t)
+        if len(nodes) == 0 and reasons is not None:
+            why = reasons(p)
+            if why:
+                log.info("0/%d nodes are available for Pod: %s: %s", n_nodes, ref, why)
         tables.append(t)
     return tables

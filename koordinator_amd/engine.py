@@ -63,6 +63,63 @@ def row_eval(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray, now_ns:
     return bool(f.value), a.value, b.value, c.value
 
 
+def row_why(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray, now_ns: int, first_fail: bool = False) -> int:
+    """kg_row_why: the reason word (nat.WHY_*) of one pair on host rows; 0 ⇔ feasible.  Ignores elig_class."""
+    w = ctypes.c_uint32(0)
+    _check(nat.lib().kg_row_why(nat.ptr(cfg), nat.ptr(node_row), nat.ptr(pod_row), int(now_ns),
+                                nat.DIAG_FIRST_FAIL if first_fail else 0, ctypes.byref(w)), what="kg_row_why")
+    return int(w.value)
+
+
+# the reference's reason strings: upstream NodeResourcesFit ("Too many pods", "Insufficient <resource>"),
+# LoadAwareScheduling (load_aware.go:45, resource not named: the word holds the plugin's verdict alone) and
+# NodeNUMAResource (frameworkext/topologymanager/manager.go:70)
+REASON_ABSENT = "node(s) not in the snapshot"
+REASON_ELIG = "node(s) didn't match the pod's eligibility class"
+REASON_FIT_PODS = "Too many pods"
+REASON_LOADAWARE = "node(s) usage exceed threshold"
+REASON_NUMA = "node(s) NUMA Topology affinity error"
+
+
+def resource_names(cfg: np.ndarray) -> list:
+    """The name of each resource id: the fixed ones, then the named slots from ext_resource_names."""
+    ext = [bytes(b).split(b"\0")[0].decode() for b in np.asarray(cfg["ext_resource_names"]).reshape(-1)]
+    return list(nat.FIXED_RES_NAMES) + [n or f"ext{i}" for i, n in enumerate(ext)]
+
+
+def why_names(cfg: np.ndarray, word: int) -> list:
+    """The reference's reason strings of a reason word (or of a counts slot index via 1 << slot), in the filter
+    order: absent, eligibility, NodeResourcesFit ("Too many pods", "Insufficient <resource>" per failing resource,
+    the named slots by their ext_resource_names), LoadAwareScheduling, NodeNUMAResource."""
+    word = int(word)
+    out = []
+    if word & nat.WHY_ABSENT:
+        out.append(REASON_ABSENT)
+    if word & nat.WHY_ELIG:
+        out.append(REASON_ELIG)
+    if word & nat.WHY_FIT_PODS:
+        out.append(REASON_FIT_PODS)
+    names = resource_names(cfg)
+    for r in range(nat.NUM_RES):
+        if word & nat.WHY_FIT_RES(r):
+            out.append("Insufficient " + names[r])
+    if word & nat.WHY_LOADAWARE:
+        out.append(REASON_LOADAWARE)
+    if word & nat.WHY_NUMA:
+        out.append(REASON_NUMA)
+    return out
+
+
+def why_histogram(cfg: np.ndarray, counts_row) -> str:
+    """One pod's counts as the FailedScheduling event lists them: "312 Insufficient cpu, 97 Too many pods, ..."."""
+    parts = []
+    for b in range(nat.WHY_SLOT_REJECTED):
+        c = int(counts_row[b])
+        if c:
+            parts += [f"{c} {s}" for s in why_names(cfg, 1 << b)]
+    return ", ".join(parts)
+
+
 def row_eval_rsv(cfg: np.ndarray, node_row: np.ndarray, rsv: np.ndarray, pod_row: np.ndarray, now_ns: int):
     """(feasible, fit, la, numa, raw, order, nominated) of one pair with the node's reservation slots
     (host rows)."""
@@ -202,6 +259,7 @@ class Engine:
         rows = np.ascontiguousarray(rows, dtype=nat.POD_ROW)
         _check(nat.lib().kg_pods_set(self._h, nat.ptr(rows), len(rows)), self, "kg_pods_set")
         self.n_pods = len(rows)
+        self._pod_rows = rows.copy() if debug.debug_top_n() else None  # the debug dump's reason lines (_why_line)
 
     def spill_count(self) -> int:
         """kg_pods_spill_count: pods of the uploaded batch outside its slot map (batch_slot_map), evaluated on the
@@ -276,8 +334,26 @@ class Engine:
         _check(nat.lib().kg_eval(self._h, int(now_ns), ctypes.byref(out)), self, "kg_eval")
         top_n = debug.debug_top_n()   # --debug-scores (frameworkext/debug.go:32-48)
         if top_n:
-            debug.dump_eval(self.cfg, res, min(self.n_nodes, self.score_stride), top_n)
+            debug.dump_eval(self.cfg, res, min(self.n_nodes, self.score_stride), top_n,
+                            reasons=lambda p: self._why_line(p, now_ns))
         return res
+
+    def _why_line(self, pod: int, now_ns: int) -> str:
+        """The reason histogram of pod `pod` of the uploaded batch (the debug dump's line for a pod without a
+        feasible node); empty where kg_diagnose does not answer (reservation slots, cpuset binding)."""
+        rows = getattr(self, "_pod_rows", None)
+        if rows is None or pod >= len(rows):
+            return ""
+        try:
+            got = self.diagnose(rows[pod:pod + 1], now_ns)
+        except EngineError:
+            return ""
+        parts = [why_histogram(self.cfg, got["counts"][0])]
+        if got["pod_why"][0] & nat.WHY_POD_QUOTA:
+            parts.append("the pod's quota is exceeded")
+        if got["pod_why"][0] & nat.WHY_POD_RSV_REQUIRED:
+            parts.append("the pod requires a reservation and none is loaded")
+        return ", ".join(p for p in parts if p)
 
     def eval_device(self, now_ns: int, mask_ptr: int = 0, scores_ptr: int = 0, top1_ptr: int = 0,
                     numa_ptr: int = 0, rsv_ptr: int = 0) -> None:
@@ -429,6 +505,41 @@ class Engine:
         _check(nat.lib().kg_cycle_one(self._h, nat.ptr(pod_row), int(now_ns), nat.CYCLE_COMMIT if commit else 0,
                                       ctypes.byref(eo), ctypes.byref(out)), self, "kg_cycle_one")
         return out
+
+    def diagnose(self, pod_rows: np.ndarray, now_ns: int, first_fail: bool = False, why: bool = False) -> dict:
+        """kg_diagnose: why the pods (at most nat.DIAG_MAX_PODS rows; they travel with the call, the batch of
+        set_pods is not touched) are rejected by the nodes of the shard, in one call.  Returns counts
+        [n][nat.WHY_SLOTS] u32 (nodes per reason bit; slots 30 / 31: rejected / feasible nodes) and pod_why [n] u32
+        (nat.WHY_POD_*), with `why` also the words [n][stride] u32 (columns as eval()'s planes).  `first_fail`: each
+        word keeps the first failing group only (what the reference's NodeToStatusMap holds).  Mutates nothing."""
+        rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+        n = len(rows)
+        res = {"counts": np.zeros((n, nat.WHY_SLOTS), dtype=np.uint32), "pod_why": np.zeros(n, dtype=np.uint32)}
+        if why:
+            res["why"] = np.zeros((n, self.score_stride), dtype=np.uint32)
+        _check(nat.lib().kg_diagnose(self._h, nat.ptr(rows) if n else None, n, int(now_ns),
+                                     nat.DIAG_FIRST_FAIL if first_fail else 0, nat.ptr(res["counts"]) if n else None,
+                                     nat.ptr(res["pod_why"]) if n else None,
+                                     nat.ptr(res["why"]) if why and res["why"].size else None, 0), self, "kg_diagnose")
+        return res
+
+    def diagnose_host(self, pod_rows: np.ndarray, now_ns: int, counts_ptr: int, pod_why_ptr: int = 0, why_ptr: int = 0,
+                      first_fail: bool = False) -> None:
+        """kg_diagnose into caller-owned host buffers (e.g. pinned memory, as eval_host): what the Go plugins'
+        PostFilter calls (INTEGRATION.md `Diagnose`)."""
+        rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+        _check(nat.lib().kg_diagnose(self._h, nat.ptr(rows), len(rows), int(now_ns),
+                                     nat.DIAG_FIRST_FAIL if first_fail else 0, counts_ptr or None, pod_why_ptr or None,
+                                     why_ptr or None, 0), self, "kg_diagnose")
+
+    def diagnose_device(self, pod_rows: np.ndarray, now_ns: int, counts_ptr: int, pod_why_ptr: int = 0, why_ptr: int = 0,
+                        first_fail: bool = False) -> None:
+        """kg_diagnose into caller-owned device buffers (16-byte aligned, any previous content), as eval_device; the
+        call returns after the launches completed."""
+        rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+        _check(nat.lib().kg_diagnose(self._h, nat.ptr(rows), len(rows), int(now_ns),
+                                     nat.DIAG_FIRST_FAIL if first_fail else 0, counts_ptr or None, pod_why_ptr or None,
+                                     why_ptr or None, 1), self, "kg_diagnose")
 
     # Reservation / ElasticQuota -----------------------------------------------------------
     def set_reservations(self, rsv: np.ndarray) -> None:
