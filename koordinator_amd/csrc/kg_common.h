@@ -15,8 +15,10 @@
 //   q = max((int)fma(-pr, R, F), 0)
 // The summed rounding error is below 2^-44.7 whenever the true value lies in [-1, 101], so
 // adding 2^-42 keeps exact integers from rounding down, and the gap 1/cap > 2^-41.8 keeps
-// non-integers from rounding up, for every cap <= 2^41.  Nodes outside those bounds get
-// KGD_SLOW and take the exact int64 path (kg_pair_exact).  MostAllocated is the same with
+// non-integers from rounding up, for every 0 < cap < 2^41, 0 <= base < 2^50 and 0 <= pr < 2^50.  The base must
+// not be negative: F is then far above 100 (below 0 for MostAllocated) while the pair value can still lie in
+// [0, 100], and F's ulp exceeds 1/cap, so the bias is lost in F's own rounding.  Nodes outside those bounds
+// (kg_val_out) get KGD_SLOW and take the exact int64 path (kg_pair_exact).  MostAllocated is the same with
 // F = RN(100*base/cap + 2^-42), q = min(q, 100).
 #pragma once
 #include <math.h>
@@ -35,7 +37,7 @@
 #define KG_BLOCK 512                // threads per eval workgroup
 #define KG_EPS 0x1p-42
 #define KG_CAP_LIMIT (1LL << 41)    // fast-path bound on every divisor
-#define KG_VAL_LIMIT (1LL << 50)    // fast-path bound on every numerator term
+#define KG_VAL_LIMIT (1LL << 50)    // fast-path bound on every numerator term (each in [0, KG_VAL_LIMIT))
 
 // derived node flags
 #define KGD_VALID 0x1u
@@ -214,6 +216,8 @@ KG_HD bool kg_elig_ok(const kg_planes &pl, const kg_pod_dev &p, int64_t node) {
 }
 
 KG_HD int64_t kg_abs64(int64_t x) { return x < 0 ? -x : x; }
+// a score base (NonZeroRequested / Requested / LoadAware usage) outside the fast path's domain [0, KG_VAL_LIMIT)
+KG_HD bool kg_val_out(int64_t base) { return base < 0 || base >= KG_VAL_LIMIT; }
 
 // Exact truncating int64 quotient and remainder of n / d (d > 0) — the device has no int64 divide
 // instruction: an fp64 estimate n · RN(1/d) (relative error ≤ 3·2^-53, so off by < |n/d|·2^-51.4 + 1 ≤ 49) is
@@ -277,7 +281,7 @@ KG_HD uint32_t kg_finalize_fit_r(const kg_consts &c, const kg_planes &pl, int64_
     if (c.fit_w[r] > 0 && present && a != 0) {
         out |= 2u;
         int64_t base = r < 2 ? row.nonzero_requested[r] : row.requested[r];
-        if (a < 0 || a >= KG_CAP_LIMIT || kg_abs64(base) >= KG_VAL_LIMIT) {
+        if (a < 0 || a >= KG_CAP_LIMIT || kg_val_out(base)) {
             out |= 1u;
         } else {
             R = 100.0 / (double)a;
@@ -303,8 +307,7 @@ KG_HD uint32_t kg_finalize_la_r(const kg_consts &c, const kg_planes &pl, int64_t
     int64_t a = row.la_alloc[r];
     double R = 0.0, F0 = 0.0, F1 = 0.0;
     if (a != 0) {
-        if (a < 0 || a >= KG_CAP_LIMIT || kg_abs64(row.la_used[0][r]) >= KG_VAL_LIMIT ||
-            kg_abs64(row.la_used[1][r]) >= KG_VAL_LIMIT) {
+        if (a < 0 || a >= KG_CAP_LIMIT || kg_val_out(row.la_used[0][r]) || kg_val_out(row.la_used[1][r])) {
             slow = 3u;
         } else {
             R = 100.0 / (double)a;
@@ -336,8 +339,7 @@ KG_HD bool kg_finalize_lax_r(const kg_consts &c, const kg_planes &pl, int64_t i,
     const int64_t a = row.la_alloc_x[x];
     double R = 0.0, F0 = 0.0, F1 = 0.0;
     if (c.la_wx[x] > 0 && a != 0) {
-        if (a < 0 || a >= KG_CAP_LIMIT || kg_abs64(row.la_used_x[0][x]) >= KG_VAL_LIMIT ||
-            kg_abs64(row.la_used_x[1][x]) >= KG_VAL_LIMIT) {
+        if (a < 0 || a >= KG_CAP_LIMIT || kg_val_out(row.la_used_x[0][x]) || kg_val_out(row.la_used_x[1][x])) {
             slow = true;
         } else {
             R = 100.0 / (double)a;

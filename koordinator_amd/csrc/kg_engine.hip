@@ -3119,7 +3119,7 @@ __global__ __launch_bounds__(KG_RESOLVE_THREADS) void k_resolve(kg_consts c, kg_
             bool bounds = false;
             double R = 0.0, F = 0.0;
             if (a != 0) {
-                if (a < 0 || a >= KG_CAP_LIMIT || kg_abs64(u0) >= KG_VAL_LIMIT || kg_abs64(u1) >= KG_VAL_LIMIT) {
+                if (a < 0 || a >= KG_CAP_LIMIT || kg_val_out(u0) || kg_val_out(u1)) {
                     bounds = true;
                 } else {
                     R = 100.0 / (double)a;
