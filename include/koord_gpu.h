@@ -638,6 +638,10 @@ kg_status kg_sync(kg_engine *eng);
 
 /* Node snapshot (HBM-resident). */
 kg_status kg_snapshot_reset(kg_engine *eng, int32_t n_nodes);
+/* kg_snapshot_upsert writes rows[k] to node node_index[k], k < n, and derives the node's planes from it.  The
+ * entries apply in order: where one call names an index more than once, the last entry for that index wins (row,
+ * planes and cpuset-binding facts alike) and the earlier ones leave no trace.  Every entry is validated, superseded
+ * ones included; an invalid one fails the call and changes nothing.  n = 0 is a no-op. */
 kg_status kg_snapshot_upsert(kg_engine *eng, const int32_t *node_index, const kg_node_row *rows, int32_t n);
 kg_status kg_snapshot_remove(kg_engine *eng, int32_t node_index);
 kg_status kg_snapshot_download(kg_engine *eng, int32_t first, int32_t n, kg_node_row *out);

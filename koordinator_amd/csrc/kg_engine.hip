@@ -4848,6 +4848,31 @@ kg_status kg_snapshot_upsert(kg_engine *e, const int32_t *node_index, const kg_n
             return set_err(e, KG_ERR_UNSUPPORTED, "node %d: a CPU bind policy without CPU detail", node_index[k]);
         facts[k] = f;
     }
+    // an index named more than once: the entries apply in order, so the last one wins (koord_gpu.h).  Only that
+    // entry is staged: k_upsert runs one thread per staged row, and two threads on one node would race between the
+    // stored row and the planes derived from it
+    std::vector<int32_t> uniq_index;
+    std::vector<kg_node_row> uniq_rows;
+    bool ascending = true;   // (a snapshot load, a sorted flush: no index can repeat)
+    for (int32_t k = 1; k < n && ascending; k++) ascending = node_index[k] > node_index[k - 1];
+    if (!ascending) {
+        std::unordered_map<int32_t, int32_t> last;
+        last.reserve((size_t)n);
+        for (int32_t k = 0; k < n; k++) last[node_index[k]] = k;
+        if ((int32_t)last.size() != n) {
+            std::vector<uint8_t> uniq_facts;
+            for (int32_t k = 0; k < n; k++) {
+                if (last[node_index[k]] != k) continue;
+                uniq_index.push_back(node_index[k]);
+                uniq_rows.push_back(rows[k]);
+                uniq_facts.push_back(facts[(size_t)k]);
+            }
+            facts.swap(uniq_facts);
+            node_index = uniq_index.data();
+            rows = uniq_rows.data();
+            n = (int32_t)uniq_index.size();
+        }
+    }
     for (int32_t k = 0; k < n; k++) {
         uint8_t &old = e->node_bind_facts[node_index[k]];
         e->n_numa_policy_nodes += (int)(facts[k] & 1) - (int)(old & 1);

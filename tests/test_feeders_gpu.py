@@ -39,6 +39,9 @@ def test_feeder_deltas_drive_engine_and_match_oracle(numa):
                                                 phase="Pending")) for i in range(64)]
         view = cl.view(extra_pods=pend)
         idx = np.array([view.pod_index(p) for p in pend], dtype=np.int32)
+        # the incrementally fed engine itself (capacity 4096, the planes the 40 steps of deltas left behind)
+        eng.set_pods(engine.build_pod_rows(cfg, view, idx))
+        fed = eng.eval(cl.now_ns)
         eng.load_snapshot(got)                                      # exactly the fed nodes, no spare capacity
         eng.set_pods(engine.build_pod_rows(cfg, view, idx))
         res = eng.eval(cl.now_ns)
@@ -47,8 +50,20 @@ def test_feeder_deltas_drive_engine_and_match_oracle(numa):
     if numa:
         m, fit, la, nm = oracle.eval_matrix3(cfg, view, idx, cl.now_ns)
         np.testing.assert_array_equal(res["numa_scores"][:, :N], nm)
+        np.testing.assert_array_equal(fed["numa_scores"][:, :N], nm)
     else:
         m, fit, la = oracle.eval_matrix(cfg, view, idx, cl.now_ns)
+    fed_mask = engine.unpack_mask(fed["mask"], cap)
+    np.testing.assert_array_equal(fed_mask[:, :N], m)
+    assert not fed_mask[:, N:].any()                                # never-fed capacity: no pod is feasible there
+    np.testing.assert_array_equal(fed["scores"][:, :N, 0], fit)
+    np.testing.assert_array_equal(fed["scores"][:, :N, 1], la)
+    w = [int(cfg[k]) for k in ("weight_fit", "weight_loadaware", "weight_numa")]
+    total = w[0] * fit.astype(np.int64) + w[1] * la.astype(np.int64) + (w[2] * nm.astype(np.int64) if numa else 0)
+    total = np.where(m, total, -1)
+    best_node, best_total = engine.decode_top1(fed["top1"])
+    np.testing.assert_array_equal(best_total, total.max(axis=1))
+    np.testing.assert_array_equal(best_node, np.where(total.max(axis=1) >= 0, total.argmax(axis=1), -1))
     np.testing.assert_array_equal(engine.unpack_mask(res["mask"], N), m)
     np.testing.assert_array_equal(res["scores"][:, :N, 0], fit)
     np.testing.assert_array_equal(res["scores"][:, :N, 1], la)
