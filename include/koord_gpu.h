@@ -393,7 +393,12 @@ typedef struct kg_reservation {
     int32_t n_assigned;            /* len(AssignedPods) */
     uint32_t owner_classes;        /* bit c ⇔ Match(pod) for pods of owner class c */
     uint32_t affinity_classes;     /* bit a ⇔ a reservation-affinity class a selects this reservation */
-    int64_t order;                 /* label scheduling.koordinator.sh/reservation-order (0 ⇔ absent / unparsable) */
+    /* label scheduling.koordinator.sh/reservation-order as strconv.ParseInt(s, 10, 64) reads it (scoring.go:166-178);
+     * 0 ⇔ absent / unparsable.  Domain: every int64.  Negative orders are admitted and precede the positive ones
+     * (the smallest non-zero order wins).  0 and INT64_MAX never win: "order != 0 && selectOrder > order" starts
+     * from selectOrder = MaxInt64, so a label of 9223372036854775807 reads like no label — INT64_MAX is also the
+     * engine's "no order" value, with the same meaning. */
+    int64_t order;
     kg_resource_list allocatable;  /* Allocatable; present = ResourceNames */
     kg_resource_list allocated;    /* Allocated */
 } kg_reservation;

@@ -3939,6 +3939,9 @@ void cls_prepare(kg_engine *e) {
     e->cls_reps.clear();
     const bool la_on = (e->cfg.enabled_plugins & KG_PLUGIN_LOADAWARE) != 0;
     if (la_on && e->consts.la_shift == 0xFF) return;
+    // neither Fit nor LoadAware (Reservation alone): launch_cls has no form without both (its Fit-less form scores
+    // LoadAware), so the batch takes the slot kernels, whose generic form leaves a disabled plugin's plane at 0
+    if (!la_on && !(e->cfg.enabled_plugins & KG_PLUGIN_FIT)) return;
     std::map<ClsKey, int> index;
     std::vector<ClsKey> keys;
     std::vector<std::vector<int32_t>> members;

@@ -1478,8 +1478,11 @@ static int rsv_usable(const kg_reservation *r) { /* transformer.go:116-124 */
     return 1;
 }
 static int rsv_match(const kg_pod_spec *pod, const kg_reservation *r) { /* matchReservation :348-372 */
-    if (pod->rsv_owner_class < 0 || !((r->owner_classes >> pod->rsv_owner_class) & 1u)) return 0;
-    if (pod->rsv_affinity_class >= 0 && !((r->affinity_classes >> pod->rsv_affinity_class) & 1u)) return 0;
+    /* classes are bits of a 32-bit mask: a class outside 0..31 matches nothing (and must not reach the shift) */
+    if (pod->rsv_owner_class < 0 || pod->rsv_owner_class > 31 || !((r->owner_classes >> pod->rsv_owner_class) & 1u)) return 0;
+    if (pod->rsv_affinity_class >= 0 &&
+        (pod->rsv_affinity_class > 31 || !((r->affinity_classes >> pod->rsv_affinity_class) & 1u)))
+        return 0;
     return 1;
 }
 
@@ -1657,7 +1660,8 @@ static int quota_inputs_valid(const kg_config *c, const kg_cluster_view *v, cons
         int32_t a = g, d = 0;
         while (a >= 0) {
             const int32_t up = v->quotas[a].parent;
-            if (up < -1 || up >= n || up == a || ++d > KG_QUOTA_MAX_DEPTH) return -2;
+            /* d counts ancestors: a group may have KG_QUOTA_MAX_DEPTH of them, as kg_quota_set admits */
+            if (up < -1 || up >= n || up == a || (up >= 0 && ++d > KG_QUOTA_MAX_DEPTH)) return -2;
             a = up;
         }
     }
