@@ -27,6 +27,14 @@
  *                           Reserve) for a queue of pods, with Reserve deltas of LoadAware.Reserve
  *                           (load_aware.go:260-267) and NodeInfo.AddPod (mirror reservation/transformer.go:293-306)
  *   kg_commit               one Reserve (AssumePod + LoadAware.Reserve) of a pod on a node
+ *   kg_unreserve            the plugins' Unreserve, run by the framework when Permit, PreBind or Bind fails after
+ *   / kg_row_unreserve      Reserve (under Coscheduling for a whole gang at once): LoadAware podAssignCache.unAssign
+ *                           (loadaware/load_aware.go:265, pod_assign_cache.go:70-80), NodeNUMAResource
+ *                           resourceManager.Release → NodeAllocation.release (nodenumaresource/plugin.go:421,
+ *                           node_allocation.go:105-131), Reservation forgetPod → ReservationInfo.RemoveAssignedPod
+ *                           (reservation/plugin.go:552-574, frameworkext/reservation_info.go:390-401), ElasticQuota
+ *                           GroupQuotaManager.UnreservePod (elasticquota/plugin.go:339-351,
+ *                           core/group_quota_manager.go:799-805), and NodeInfo.RemovePod of ForgetPod
  *   kg_cycle_one            one pass of upstream scheduleOne for one pod in one launch: Filter + Score over every
  *                           node, selectHost, and (KG_CYCLE_COMMIT) the Reserve of the chosen node
  *   kg_rsv_set              reservation cache feed (reservation/cache.go:249-269 forEachAvailableReservationOnNode,
@@ -587,6 +595,26 @@ kg_status kg_build_node_rows(const kg_config *cfg, const kg_cluster_view *view,
 /* Reserve delta (AssumePod + LoadAware.Reserve + NodeNUMAResource.Reserve zone allocations) applied
  * to a host-side row. */
 kg_status kg_row_commit(const kg_config *cfg, kg_node_row *node, const kg_pod_row *pod);
+/* Unreserve on a host row: the inverse of kg_row_commit.  Subtracts exactly what the Reserve added - requested[r],
+ * nonzero_requested, pod_count - 1, the LoadAware terms la_used / la_used_x (the prod terms for a KG_POD_PROD pod) -
+ * with plain int64 subtraction, no clamp.  KG_ERR_STATE (nothing changed) when the row is not KG_NODE_VALID or holds
+ * no pod.
+ * zone_release ([KG_MAX_ZONES][2] by zone slot, or NULL; KG_PLUGIN_NUMA only) is the pod's recorded zone allocation
+ * (PodAllocation.NUMANodeResources; kg_row_numa_alloc at Reserve time).  NodeAllocation.release: for a zone z < n_zones
+ * that has an allocation entry (either of its zone_alloc_keys bits) and each r with zone_release[z][r] > 0,
+ * zone_allocated[z][r] = max(0, zone_allocated[z][r] - release) and bit 2z + r of zone_alloc_keys is set
+ * (quotav1.SubtractWithNonNegativeResult).  Key bits are never cleared (the reference keeps the entry with zero
+ * quantities), a zone without an entry is untouched, and the row's cpuset counts are not touched.
+ * KG_ERR_INVALID_ARG (nothing changed): a negative amount, a non-zero amount at z >= n_zones, or a non-NULL
+ * zone_release with NodeNUMAResource disabled. */
+kg_status kg_row_unreserve(const kg_config *cfg, kg_node_row *node, const kg_pod_row *pod,
+                           const int64_t *zone_release /* [KG_MAX_ZONES][2] or NULL */);
+/* The zone amounts kg_row_commit would record for this pod on this (pre-Reserve) row, by zone slot: all zero where
+ * the commit records nothing.  The row is not modified.  A caller that drives Reserve itself keeps the result as the
+ * pod's PodAllocation.NUMANodeResources and hands it to kg_row_unreserve / kg_unreserve.  KG_ERR_UNSUPPORTED for a
+ * pair that binds a cpuset (kg_row_reserve). */
+kg_status kg_row_numa_alloc(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *pod,
+                            int64_t *zone_alloc /* [KG_MAX_ZONES][2], by zone slot */);
 /* Filter + Score of one (pod, node) pair on host rows, through the same per-pair code the kernels
  * run: the single-node checks of a scheduling cycle (RunFilterPluginsWithNominatedPods for one
  * node, preemption's SelectVictimsOnNode, framework_extender.go:354-372) without a device.
@@ -652,8 +680,8 @@ kg_status kg_snapshot_remove(kg_engine *eng, int32_t node_index);
 kg_status kg_snapshot_download(kg_engine *eng, int32_t first, int32_t n, kg_node_row *out);
 /* Snapshot generation (SURVEY §5 error contract; replaces the Go cache's generation check in
  * Cache.UpdateSnapshot, a per-cycle staleness test): the count of successful snapshot mutations —
- * kg_snapshot_reset, kg_snapshot_upsert / _remove, kg_commit, a committing kg_cycle_one and each placement resolve (kg_place,
- * kg_place_chunk_resolve).  After a HIP error the device state is stale: this returns KG_ERR_STATE (with
+ * kg_snapshot_reset, kg_snapshot_upsert / _remove, kg_commit, a committing kg_cycle_one, a kg_unreserve that released
+ * an entry and each placement resolve (kg_place, kg_place_chunk_resolve).  After a HIP error the device state is stale: this returns KG_ERR_STATE (with
  * the generation reached), every other entry point fails with KG_ERR_STATE, and the caller falls back to
  * the CPU plugins until kg_snapshot_reset + upsert reload the snapshot. */
 kg_status kg_snapshot_generation(kg_engine *eng, uint64_t *out);
@@ -826,6 +854,40 @@ kg_status kg_quota_download(kg_engine *eng, kg_quota *out, int32_t n);
 /* Single Reserve on the device snapshot (pod = index in the uploaded batch); a cpuset pod takes its CPUs
  * from the node's kg_cpus_set table.  KG_NOT_FOUND ⇔ its Allocate fails (nothing changed). */
 kg_status kg_commit(kg_engine *eng, int32_t pod, int32_t node);
+
+/* Batched Unreserve on the device snapshot: entry i undoes the Reserve of pods[i] on nodes[i] (kg_commit, a committing
+ * kg_cycle_one, a kg_place / kg_place_sharded placement).  The pod rows travel with the call (as kg_cycle_one and
+ * kg_diagnose); the batch uploaded with kg_pods_set is neither read nor replaced.  Node indices are global and the
+ * shard is ignored (as kg_commit).  Entries may repeat a node, a reservation slot or a quota group; the result is the
+ * same as applying the entries one by one in call order.
+ * Node part: kg_row_unreserve (with zone_release + i * KG_MAX_ZONES * 2 when given) on the node's row, then every
+ * plane and flag re-derived as kg_snapshot_upsert would from the new row.  A node is all-or-nothing: when it is not
+ * valid (removed), holds fewer pods than the call releases from it, or one of its entries names an invalid slot, none
+ * of its entries is applied and each gets released[i] = 0; the other nodes proceed (released[i] = 1).
+ * Reservation part (Reservation enabled, slots loaded, rsv_slot[i] >= 0: the kg_rsv_set index the Reserve nominated,
+ * kg_row_eval_rsv's *nominated): with m = numa_request_present & allocatable.present, allocated.v[q] =
+ * max(0, allocated.v[q] - numa_request[q]) for q in m, allocated.present |= m, n_assigned - 1.  A slot is invalid for
+ * an entry when its node is not nodes[i] or its n_assigned is smaller than the number of entries naming it.
+ * ElasticQuota part (released entries only): numa_request subtracted from `used` of the pod's group and every
+ * ancestor, and from non_preemptible_used for a KG_POD_NON_PREEMPTIBLE pod.
+ * Errors (nothing launched, nothing changed): KG_ERR_INVALID_ARG for n < 0, a null pods / nodes / released with n > 0,
+ * flags != 0, or zone arguments kg_row_unreserve refuses; KG_ERR_RANGE for n > KG_UNRESERVE_MAX, a node outside the
+ * snapshot, a slot at or past the loaded count, or a pod row outside the engine bounds; KG_ERR_STATE without a
+ * snapshot, on a stale engine, for a quota index without a kg_quota_set group, or rsv_slot[i] >= 0 with no slots
+ * loaded; KG_ERR_UNSUPPORTED under NodeNUMAResource for a pod with KG_POD_NUMA_CPU_BIND or a snapshot holding a node
+ * with a CPU bind policy (kg_cycle_one's rule: a cpuset release needs the CPU table; those cycles keep
+ * kg_snapshot_upsert + kg_cpus_set).
+ * On success: n = 0 is a no-op; the generation goes up by 1 when at least one entry was released; kg_counters.placed
+ * is unchanged, h2d_bytes grows by the bytes uploaded; the call returns after the launches completed.
+ * Under kg_place_sharded every rank calls it with the same arguments, so the replicas stay identical.
+ * Contract: the release is exact for a Reserve whose node row the engine still holds.  After a kg_snapshot_upsert of
+ * that node the host row is the truth (it was built without the pod, or the caller rebuilds it so): the caller must
+ * not also release. */
+#define KG_UNRESERVE_MAX 4096
+kg_status kg_unreserve(kg_engine *eng, const kg_pod_row *pods, const int32_t *nodes, int32_t n, uint32_t flags,
+                       const int64_t *zone_release /* [n][KG_MAX_ZONES][2] or NULL */,
+                       const int32_t *rsv_slot     /* [n], kg_rsv_set index or -1; or NULL */,
+                       uint8_t *released           /* [n] out, host */);
 
 /* One scheduling cycle of one pod (upstream scheduleOne: Filter and Score over every node of the shard,
  * selectHost, Reserve) as ONE kernel launch and ONE stream synchronisation: the per-pod loop of the Go plugins

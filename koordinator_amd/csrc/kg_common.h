@@ -1704,6 +1704,68 @@ KG_HD void kg_quota_commit(kg_quota *qs, int32_t g, const kg_pod_dev &p) {
     }
 }
 
+// ---- Unreserve (kg_row_unreserve, kg_unreserve) ----------------------------------------------
+// The inverses of the Reserve deltas above, as the reference's Unreserve runs them when Permit / PreBind / Bind
+// fails after Reserve.  The node part and the quota part are plain int64 subtractions (NodeInfo.RemovePod,
+// podAssignCache.unAssign, GroupQuotaManager.UnreservePod → updateGroupDeltaUsedNoLock with the negated request);
+// the zone and reservation parts clamp at zero (quotav1.SubtractWithNonNegativeResult in NodeAllocation.release,
+// node_allocation.go:105-131, and ReservationInfo.RemoveAssignedPod, reservation_info.go:390-401).
+KG_HD void kg_apply_unreserve(kg_node_row &row, const kg_pod_dev &p) {
+    for (int r = 0; r < KG_NUM_RES; r++) row.requested[r] -= p.req[r];
+    row.nonzero_requested[0] -= p.nonzero[0];
+    row.nonzero_requested[1] -= p.nonzero[1];
+    row.pod_count -= 1;
+    row.la_used[0][0] -= p.la_est_i[0];
+    row.la_used[0][1] -= p.la_est_i[1];
+    if (p.flags & KG_POD_PROD) {
+        row.la_used[1][0] -= p.la_est_i[0];
+        row.la_used[1][1] -= p.la_est_i[1];
+    }
+    for (int r = 0; r < KG_NUM_RES - 2; r++) {
+        row.la_used_x[0][r] -= p.la_est_x[r];
+        if (p.flags & KG_POD_PROD) row.la_used_x[1][r] -= p.la_est_x[r];
+    }
+}
+// max(0, have − release) for release > 0, without leaving int64 on a negative `have`
+KG_HD int64_t kg_sub_nonneg(int64_t have, int64_t release) { return have > release ? have - release : 0; }
+// zone z's allocation has an entry (the reference keeps the entry, with zero quantities, once it exists)
+KG_HD bool kg_zone_has_entry(const kg_node_row &row, int z) { return ((row.zone_alloc_keys >> (2 * z)) & 3u) != 0; }
+// one pod's zone release (`rel`: [KG_MAX_ZONES][2] by zone slot, amounts ≥ 0) on the row
+KG_HD void kg_zone_release(kg_node_row &row, const int64_t *rel) {
+    for (int z = 0; z < KG_MAX_ZONES && z < row.n_zones; z++) {
+        if (!kg_zone_has_entry(row, z)) continue;
+        for (int r = 0; r < 2; r++) {
+            const int64_t d = rel[2 * z + r];
+            if (d <= 0) continue;
+            row.zone_allocated[z][r] = kg_sub_nonneg(row.zone_allocated[z][r], d);
+            row.zone_alloc_keys |= 1u << (2 * z + r);
+        }
+    }
+}
+// ReservationInfo.RemoveAssignedPod: Allocated = SubtractWithNonNegativeResult(Allocated, Mask(requests, ResourceNames))
+KG_HD void kg_rsv_uncommit(kg_reservation &r, const kg_pod_dev &p) {
+    const uint32_t m = p.numa_present & r.allocatable.present;
+    for (int q = 0; q < KG_NUM_RES; q++)
+        if ((m >> q) & 1u) {
+            const int64_t v = kg_rl_get(r.allocated, q) - p.numa_req[q];
+            r.allocated.v[q] = v > 0 ? v : 0;
+        }
+    r.allocated.present |= m;
+    r.n_assigned -= 1;
+}
+KG_HD void kg_rl_sub_pod(kg_resource_list &l, const kg_pod_dev &p) {
+    for (int q = 0; q < KG_NUM_RES; q++)
+        if ((p.numa_present >> q) & 1u) l.v[q] = kg_rl_get(l, q) - p.numa_req[q];
+    l.present |= p.numa_present;
+}
+// UnreservePod → updateGroupDeltaUsedNoLock: the group and all its ancestors (the chain kg_quota_commit walks)
+KG_HD void kg_quota_uncommit(kg_quota *qs, int32_t g, const kg_pod_dev &p) {
+    for (int32_t a = g, d = 0; a >= 0 && d <= KG_QUOTA_MAX_DEPTH; a = qs[a].parent, d++) {
+        kg_rl_sub_pod(qs[a].used, p);
+        if (p.flags & KG_POD_NON_PREEMPTIBLE) kg_rl_sub_pod(qs[a].non_preemptible_used, p);
+    }
+}
+
 // ---- rejection reasons (kg_row_why, kg_diagnose) --------------------------------------------
 // The reason word of one (pod, node) pair (KG_WHY_*): every enabled Filter plugin evaluated on its own, zero
 // exactly when the pair is feasible.  NodeResourcesFit reports every failing resource (upstream fitsRequest

@@ -83,6 +83,9 @@
 //                                     mask words, tile keys, top-k tile keys
 //   113-115 k_why                     pod row (read), reason plane, per-(pod, tile) partial counts
 //   116-118 k_why_reduce              partial counts (read), counts, pod-level words
+//   119-124 k_unreserve               node group, node (row and planes), entry range, reservation node, slot range,
+//                                     released (call index)
+//   125-126 k_unreserve_quota         released (call index, read), quota group of a chain
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -3240,6 +3243,217 @@ __global__ void k_commit_one(kg_consts c, kg_planes pl, const kg_pod_dev *__rest
 }
 
 // ---------------------------------------------------------------------------------------
+// kg_unreserve: the Unreserve of a batch of (pod, node) entries
+// ---------------------------------------------------------------------------------------
+// The host groups the entries stably by node (call order inside a node) and uploads them in that order, so a node's
+// entries are the contiguous range [first[b], first[b + 1]).  k_unreserve runs one 64-thread workgroup (one wave) per
+// distinct node, without atomics or cross-workgroup traffic: the canonical row is staged in LDS, the verdict (valid
+// row, enough pods, valid slots) is workgroup-uniform, and then one lane per part subtracts its entries' sum from its
+// field of the row and derives that part's planes with the very functions kg_finalize_node is made of
+// (kg_finalize_fit_r / _la_r / _lax_r on the LDS row), as the placement resolve's Reserve does:
+//   lanes 0..11   resource r: requested (and nonzero_requested for cpu / memory), the Fit planes, the over-* flags
+//   lanes 12..13  LoadAware cpu / memory: both usage terms and their planes
+//   lanes 14..23  LoadAware extra resource x: both usage terms and, under extra weights, their planes
+//   lanes 24..39  (zone, resource): the clamped zone release, entry by entry in call order
+//   lane  40      the pod count and the pods-full flag
+//   lanes 41..56  one reservation slot of the node each (a slot belongs to one node: no other workgroup touches it)
+// Plain int64 subtraction commutes, so subtracting a part's sum equals releasing the entries one by one; the clamped
+// parts (zones, reservation slots) walk their entries in order.  After a barrier lane 0 builds dflags and fit_mask
+// from the parts' results (kg_dflags_dynamic, a reservation node keeping its KGD_RSV form as in kg_finalize_flags).
+struct UnrArgs {
+    const kg_pod_dev *pods;   // [n] the entries' pod rows, grouped by node
+    const int32_t *node;      // [nd] the distinct nodes
+    const int32_t *first;     // [nd + 1] first entry of each
+    const int32_t *orig;      // [n] call index of each grouped entry
+    const int64_t *zrel;      // [n][KG_MAX_ZONES * 2] zone releases, grouped (nullptr: none)
+    const int32_t *slot;      // [n] reservation slot (device order) or −1, grouped (nullptr: no reservation part)
+    uint8_t *released;        // [n] by call index
+    int32_t n, nd, n_nodes, n_rsv;
+};
+#define KG_UNR_LA0 KG_NUM_RES
+#define KG_UNR_LAX0 (KG_NUM_RES + 2)
+#define KG_UNR_ZONE0 (2 * KG_NUM_RES)
+#define KG_UNR_PODS (KG_UNR_ZONE0 + 2 * KG_MAX_ZONES)
+#define KG_UNR_RSV0 (KG_UNR_PODS + 1)
+static_assert(KG_UNR_RSV0 + KG_MAX_RSV_PER_NODE <= 64, "k_unreserve: one lane per part of a node");
+
+__global__ __launch_bounds__(64) void k_unreserve(kg_consts c, kg_planes pl, RsvArgs ra, UnrArgs a) {
+    constexpr int ROW_U4 = (int)(sizeof(kg_node_row) / 16);
+    static_assert(sizeof(kg_node_row) % 16 == 0, "rows are staged as 16-byte words");
+    __shared__ __attribute__((aligned(16))) kg_node_row srow;
+    __shared__ uint32_t fin[2 * KG_NUM_RES];   // kg_finalize_fit_r | kg_finalize_la_r | kg_finalize_lax_r results
+    __shared__ uint32_t fl_over[3], fl_pods_full, zkey[2 * KG_MAX_ZONES];
+    __shared__ int32_t s_bad;
+    const int tid = threadIdx.x;
+    const int32_t b = (int32_t)blockIdx.x;
+    if (!KG_IN(119, b, a.nd)) return;
+    const int32_t node = a.node[b], e0 = a.first[b], e1 = a.first[b + 1];
+    if (!KG_IN(120, node, a.n_nodes) || !KG_IN(121, e0, a.n + 1) || !KG_IN(121, e1, a.n + 1) || e1 < e0) return;
+    for (int x = tid; x < ROW_U4; x += 64)
+        reinterpret_cast<uint4 *>(&srow)[x] = reinterpret_cast<const uint4 *>(pl.rows + node)[x];
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    // the node's verdict: all of its entries or none
+    const int32_t cnt = e1 - e0;
+    bool bad = !(srow.flags & KG_NODE_VALID) || (int64_t)srow.pod_count < (int64_t)cnt;
+    const bool rsv_on = a.slot != nullptr && ra.rsv != nullptr;
+    int32_t rf0 = 0, rf1 = 0;   // the node's slots
+    if (rsv_on) {
+        const int32_t k = pl.rsv_of ? pl.rsv_of[node] : -1;
+        if (k >= 0 && KG_IN(122, k, ra.n_rn)) {
+            rf0 = ra.rfirst[k];
+            rf1 = ra.rfirst[k + 1];
+            if (!KG_IN(123, rf0, a.n_rsv + 1) || !KG_IN(123, rf1, a.n_rsv + 1) || rf1 - rf0 > KG_MAX_RSV_PER_NODE) rf0 = rf1 = 0;
+        }
+        for (int32_t i = e0 + tid; i < e1; i += 64) {   // a slot on another node
+            const int32_t s = a.slot[i];
+            if (s >= 0 && (s < rf0 || s >= rf1)) bad = true;
+        }
+        if (tid < rf1 - rf0) {   // a slot named by more entries than it has assigned pods
+            const int32_t s = rf0 + tid;
+            int32_t named = 0;
+            for (int32_t i = e0; i < e1; i++) named += a.slot[i] == s ? 1 : 0;
+            if (ra.rsv[s].n_assigned < named) bad = true;
+        }
+    }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    if (s_bad) {
+        for (int32_t i = e0 + tid; i < e1; i += 64)
+            if (KG_IN(124, a.orig[i], a.n)) a.released[a.orig[i]] = 0;
+        return;
+    }
+    kg_node_row &row = pl.rows[node];
+    if (tid < KG_NUM_RES) {
+        const int r = tid;
+        uint64_t d = 0, dz = 0;
+        for (int32_t i = e0; i < e1; i++) {
+            d += (uint64_t)a.pods[i].req[r];
+            if (r < 2) dz += (uint64_t)a.pods[i].nonzero[r];
+        }
+        const int64_t req = (int64_t)((uint64_t)srow.requested[r] - d);
+        srow.requested[r] = req;
+        row.requested[r] = req;
+        if (r < 2) {
+            const int64_t nz = (int64_t)((uint64_t)srow.nonzero_requested[r] - dz);
+            srow.nonzero_requested[r] = nz;
+            row.nonzero_requested[r] = nz;
+        }
+        if (r < 3) fl_over[r] = srow.alloc[r] - req < 0 ? 1u : 0u;
+        fin[r] = kg_finalize_fit_r(c, pl, node, srow, r);
+    } else if (tid < KG_UNR_LAX0) {
+        const int r = tid - KG_UNR_LA0;
+        uint64_t d0 = 0, d1 = 0;
+        for (int32_t i = e0; i < e1; i++) {
+            const uint64_t est = (uint64_t)a.pods[i].la_est_i[r];
+            d0 += est;
+            if (a.pods[i].flags & KG_POD_PROD) d1 += est;
+        }
+        const int64_t u0 = (int64_t)((uint64_t)srow.la_used[0][r] - d0), u1 = (int64_t)((uint64_t)srow.la_used[1][r] - d1);
+        srow.la_used[0][r] = u0;
+        srow.la_used[1][r] = u1;
+        row.la_used[0][r] = u0;
+        row.la_used[1][r] = u1;
+        fin[KG_UNR_LA0 + r] = kg_finalize_la_r(c, pl, node, srow, r);
+    } else if (tid < KG_UNR_ZONE0) {
+        const int x = tid - KG_UNR_LAX0;
+        uint64_t d0 = 0, d1 = 0;
+        for (int32_t i = e0; i < e1; i++) {
+            const uint64_t est = (uint64_t)a.pods[i].la_est_x[x];
+            d0 += est;
+            if (a.pods[i].flags & KG_POD_PROD) d1 += est;
+        }
+        const int64_t u0 = (int64_t)((uint64_t)srow.la_used_x[0][x] - d0), u1 = (int64_t)((uint64_t)srow.la_used_x[1][x] - d1);
+        srow.la_used_x[0][x] = u0;
+        srow.la_used_x[1][x] = u1;
+        row.la_used_x[0][x] = u0;
+        row.la_used_x[1][x] = u1;
+        fin[KG_UNR_LAX0 + x] = c.la_extra && kg_finalize_lax_r(c, pl, node, srow, x) ? 1u : 0u;
+    } else if (tid < KG_UNR_PODS) {
+        // NodeAllocation.release of zone z's resource r (kg_zone_release, entry by entry: the subtraction clamps)
+        const int zr = tid - KG_UNR_ZONE0, z = zr >> 1, r = zr & 1;
+        uint32_t bit = 0;
+        if (a.zrel && (c.plugins & KG_PLUGIN_NUMA) && z < srow.n_zones && kg_zone_has_entry(srow, z)) {
+            int64_t v = srow.zone_allocated[z][r];
+            for (int32_t i = e0; i < e1; i++) {
+                const int64_t d = a.zrel[(int64_t)i * (2 * KG_MAX_ZONES) + zr];
+                if (d <= 0) continue;
+                v = kg_sub_nonneg(v, d);
+                bit = 1u << zr;
+            }
+            if (bit) row.zone_allocated[z][r] = v;
+        }
+        zkey[zr] = bit;
+    } else if (tid == KG_UNR_PODS) {
+        const int32_t pc = srow.pod_count - cnt;
+        row.pod_count = pc;
+        fl_pods_full = (int64_t)pc + 1 > (int64_t)srow.allowed_pods ? 1u : 0u;
+    } else if (rsv_on && tid >= KG_UNR_RSV0 && tid - KG_UNR_RSV0 < rf1 - rf0) {
+        const int32_t s = rf0 + (tid - KG_UNR_RSV0);   // ReservationInfo.RemoveAssignedPod, entry by entry
+        for (int32_t i = e0; i < e1; i++)
+            if (a.slot[i] == s) kg_rsv_uncommit(ra.rsv[s], a.pods[i]);
+    }
+    __syncthreads();
+    if (tid == 0) {   // kg_finalize_flags from the parts (metric and the static bits are unchanged)
+        bool slow = false, xslow = false;
+        uint32_t fmask = 0;
+        for (int r = 0; r < KG_NUM_RES; r++) slow = slow || (fin[r] & 1u);
+        xslow = slow;
+        for (int r = KG_UNR_LA0; r < KG_UNR_LAX0; r++) {
+            slow = slow || (fin[r] & 1u);
+            xslow = xslow || (fin[r] & 2u);
+        }
+        for (int x = 0; x < KG_NUM_RES - 2; x++) xslow = xslow || (fin[KG_UNR_LAX0 + x] & 1u);
+        for (int r = 0; r < KG_NUM_RES; r++)
+            if (fin[r] & 2u) fmask |= 1u << r;
+        const bool over[3] = {fl_over[0] != 0, fl_over[1] != 0, fl_over[2] != 0};
+        const uint32_t old = pl.dflags[node];
+        uint32_t dyn = kg_dflags_dynamic(fl_pods_full != 0, over, slow, xslow);
+        if (old & KGD_RSV) dyn &= ~(KGD_SLOW | KGD_XSLOW);   // kg_rsv_pair owns reservation nodes
+        pl.dflags[node] = (old & ~KGD_DYNAMIC) | dyn;
+        pl.fit_mask[node] = fmask;
+        uint32_t zk = 0;
+        for (int j = 0; j < 2 * KG_MAX_ZONES; j++) zk |= zkey[j];
+        if (zk) row.zone_alloc_keys = srow.zone_alloc_keys | zk;
+    }
+    for (int32_t i = e0 + tid; i < e1; i += 64)
+        if (KG_IN(124, a.orig[i], a.n)) a.released[a.orig[i]] = 1;
+}
+
+// The ElasticQuota part of kg_unreserve (GroupQuotaManager.UnreservePod): groups are shared across nodes, so one
+// workgroup walks the released entries' chains after k_unreserve.  Lane (list, q) owns resource q of `used` (list 0)
+// or `non_preemptible_used` (list 1) of every group, so no two lanes write one cell.  kg_quota_uncommit in three
+// passes: a value whose key is absent counts as 0 (kg_rl_get) - zero it; then the key sets; then the subtractions,
+// which commute.
+__global__ __launch_bounds__(64) void k_unreserve_quota(kg_quota *qs, int32_t n_quota, UnrArgs a) {
+    const int tid = threadIdx.x;
+    const int list = tid / KG_NUM_RES, q = tid % KG_NUM_RES;
+    for (int pass = 0; pass < 3; pass++) {
+        const bool lane_on = pass == 1 ? tid < 2 : tid < 2 * KG_NUM_RES;
+        const int ls = pass == 1 ? tid : list;
+        for (int32_t i = 0; lane_on && i < a.n; i++) {
+            if (!KG_IN(125, a.orig[i], a.n) || !a.released[a.orig[i]]) continue;
+            const kg_pod_dev &p = a.pods[i];
+            if (p.quota < 0 || (ls == 1 && !(p.flags & KG_POD_NON_PREEMPTIBLE))) continue;
+            if (pass != 1 && !((p.numa_present >> q) & 1u)) continue;
+            for (int32_t g = p.quota, d = 0; g >= 0 && d <= KG_QUOTA_MAX_DEPTH; d++) {
+                if (!KG_IN(126, g, n_quota)) break;
+                kg_resource_list &l = ls ? qs[g].non_preemptible_used : qs[g].used;
+                if (pass == 0) {
+                    if (!((l.present >> q) & 1u)) l.v[q] = 0;
+                } else if (pass == 1) {
+                    l.present |= p.numa_present;
+                } else {
+                    l.v[q] -= p.numa_req[q];
+                }
+                g = qs[g].parent;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // kg_cycle_one: the scheduling cycle of ONE pod (Filter + Score over the shard, selectHost, Reserve) in one launch
 // ---------------------------------------------------------------------------------------
 // One node per thread, 256 threads per workgroup, the pod row in the kernel arguments (wave-uniform: scalar loads).
@@ -3669,6 +3883,13 @@ struct kg_engine {
     void *diag_mem = nullptr;
     size_t diag_bytes = 0;
     void *diag_host = nullptr;
+    // kg_unreserve: the call's grouped entries on the device and the pinned block they pass through (both grown on
+    // demand), the zone count of every node's row (host mirror of kg_node_row.n_zones, which no commit changes: the
+    // zone arguments are validated before anything is launched) and the caller index → device slot map of kg_rsv_set
+    void *unr_mem = nullptr, *unr_host = nullptr;
+    size_t unr_bytes = 0, unr_host_bytes = 0;
+    std::vector<uint8_t> node_zones;
+    std::vector<int32_t> rsv_inv;
     int32_t comm_rank = 0, comm_world = 0;
     hipStream_t eval_stream = nullptr;  // kg_set_eval_stream (kg_place_chunk_eval), nullptr ⇒ stream
     // recorded on eval_stream after each kg_place_chunk_eval, one per partial buffer (keyed by its address): a chunk
@@ -4696,6 +4917,8 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->cyc_out) (void)hipHostFree(e->cyc_out);
     if (e->diag_mem) (void)hipFree(e->diag_mem);
     if (e->diag_host) (void)hipHostFree(e->diag_host);
+    if (e->unr_mem) (void)hipFree(e->unr_mem);
+    if (e->unr_host) (void)hipHostFree(e->unr_host);
     if (e->hot_lax) (void)hipFree(e->hot_lax);
     if (e->eq_pods) (void)hipFree(e->eq_pods);
     if (e->eq_perm) (void)hipFree(e->eq_perm);
@@ -4799,6 +5022,7 @@ kg_status kg_snapshot_reset(kg_engine *e, int32_t n_nodes) {
     e->rsv_g = nullptr;
     e->n_rsv = e->n_rn = 0;
     e->rsv_perm.clear();
+    e->rsv_inv.clear();
     if (e->elig_mem) HIP_TRY(e, hipFree(e->elig_mem));  // eligibility classes refer to node indices: dropped
     e->elig_mem = nullptr;
     e->elig_host.clear();
@@ -4808,6 +5032,7 @@ kg_status kg_snapshot_reset(kg_engine *e, int32_t n_nodes) {
     e->pl.cap = cap;
     e->n_nodes = n_nodes;
     e->node_bind_facts.assign((size_t)n_nodes, 0);
+    e->node_zones.assign((size_t)n_nodes, 0);
     e->cpu_tab.clear();   // CPU tables refer to node indices: dropped with the snapshot
     e->n_numa_policy_nodes = e->n_node_bind_nodes = e->n_no_detail_nodes = 0;
     e->shard_begin = 0;
@@ -4882,6 +5107,8 @@ kg_status kg_snapshot_upsert(kg_engine *e, const int32_t *node_index, const kg_n
         e->n_node_bind_nodes += (int)((facts[k] >> 1) & 1) - (int)((old >> 1) & 1);
         e->n_no_detail_nodes += (int)((facts[k] >> 2) & 1) - (int)((old >> 2) & 1);
         old = facts[k];
+        const int32_t nz = rows[k].n_zones;
+        e->node_zones[(size_t)node_index[k]] = (uint8_t)(nz < 0 ? 0 : nz > KG_MAX_ZONES ? KG_MAX_ZONES : nz);
     }
     // a new row invalidates the node's CPU table: bind_ready then asks for the matching kg_cpus_set (the feeders
     // send both together), so a cpuset Reserve never runs the accumulator on CPUs of an older row
@@ -6321,6 +6548,8 @@ kg_status kg_rsv_set(kg_engine *e, const kg_reservation *rsv, int32_t n) {
     e->n_rsv = n;
     e->n_rn = n_rn;
     e->rsv_perm = order;
+    e->rsv_inv.assign((size_t)n, 0);
+    for (int32_t k = 0; k < n; k++) e->rsv_inv[(size_t)order[(size_t)k]] = k;
     // re-derive every node's planes: reservation nodes leave the fast paths, the others rejoin
     hipLaunchKernelGGL(k_finalize_range, dim3((unsigned)((e->pl.cap + 255) / 256)), dim3(256), 0, e->stream, e->consts,
                        e->pl, (int64_t)0, e->pl.cap);
@@ -6614,6 +6843,124 @@ kg_status kg_diagnose(kg_engine *e, const kg_pod_row *pods, int32_t n, int64_t n
         if (why) HIP_TRY(e, hipMemcpyAsync(why, why_d, why_b, hipMemcpyDeviceToHost, e->stream));
     }
     HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the pinned pod rows are free for the next call)
+    return bounds_verdict(e);
+}
+
+// The Unreserve of n (pod, node) entries: grouped stably by node on the host, uploaded through the pinned block, one
+// k_unreserve workgroup per distinct node, then (quotas loaded and an entry with a group) the serial k_unreserve_quota.
+kg_status kg_unreserve(kg_engine *e, const kg_pod_row *pods, const int32_t *nodes, int32_t n, uint32_t flags,
+                       const int64_t *zone_release, const int32_t *rsv_slot, uint8_t *released) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (flags != 0) return set_err(e, KG_ERR_INVALID_ARG, "unknown kg_unreserve flags 0x%x", flags);
+    if (n < 0 || (n > 0 && (!pods || !nodes || !released))) return set_err(e, KG_ERR_INVALID_ARG, "null pods, nodes or released");
+    if (n > KG_UNRESERVE_MAX) return set_err(e, KG_ERR_RANGE, "kg_unreserve takes at most %d entries (got %d)", KG_UNRESERVE_MAX, n);
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised");
+    const uint32_t plug = e->cfg.enabled_plugins;
+    const bool numa_on = (plug & KG_PLUGIN_NUMA) != 0;
+    if (n > 0 && zone_release && !numa_on)
+        return set_err(e, KG_ERR_INVALID_ARG, "zone_release without NodeNUMAResource");
+    bool any_slot = false, any_quota = false;
+    for (int32_t i = 0; i < n; i++) {
+        const kg_pod_row &pod = pods[i];
+        if (nodes[i] < 0 || nodes[i] >= e->n_nodes) return set_err(e, KG_ERR_RANGE, "entry %d: node %d outside the snapshot", i, nodes[i]);
+        if (!kg_pod_row_in_bounds(pod)) return set_err(e, KG_ERR_RANGE, "entry %d: request outside the engine bounds", i);
+        if (rsv_slot && rsv_slot[i] >= 0) {
+            if (e->n_rsv == 0) return set_err(e, KG_ERR_STATE, "entry %d: reservation slot %d with no slots loaded (kg_rsv_set)", i, rsv_slot[i]);
+            if (rsv_slot[i] >= e->n_rsv) return set_err(e, KG_ERR_RANGE, "entry %d: reservation slot %d, have %d", i, rsv_slot[i], e->n_rsv);
+            any_slot = true;
+        }
+        if ((plug & KG_PLUGIN_ELASTICQUOTA) && pod.quota >= 0) {
+            if (pod.quota >= e->n_quota)
+                return set_err(e, KG_ERR_STATE, "entry %d: quota index %d without a kg_quota_set group (have %d)", i, pod.quota, e->n_quota);
+            any_quota = true;
+        }
+        if (numa_on && !(pod.flags & KG_POD_NUMA_SKIP) && (pod.flags & KG_POD_NUMA_CPU_BIND))
+            return set_err(e, KG_ERR_UNSUPPORTED, "entry %d: kg_unreserve does not release cpusets (the CPU table's refcounts): "
+                                                  "use kg_snapshot_upsert + kg_cpus_set", i);
+        if (zone_release && !kg_zone_release_ok(zone_release + (size_t)i * 2 * KG_MAX_ZONES, e->node_zones[(size_t)nodes[i]]))
+            return set_err(e, KG_ERR_INVALID_ARG, "entry %d: a negative zone release, or one past the node's %d zones", i,
+                           (int)e->node_zones[(size_t)nodes[i]]);
+    }
+    if (numa_on && e->n_node_bind_nodes > 0)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_unreserve does not release cpusets (a node with a CPU bind policy): use "
+                                              "kg_snapshot_upsert + kg_cpus_set");
+    if (n == 0) return KG_OK;
+    // stable grouping by node: order[] lists the call indices node by node, call order inside a node
+    std::vector<int32_t> order((size_t)n);
+    for (int32_t i = 0; i < n; i++) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return nodes[x] < nodes[y]; });
+    std::vector<int32_t> dnode, first;
+    for (int32_t k = 0; k < n; k++)
+        if (k == 0 || nodes[order[(size_t)k]] != nodes[order[(size_t)k - 1]]) {
+            dnode.push_back(nodes[order[(size_t)k]]);
+            first.push_back(k);
+        }
+    first.push_back(n);
+    const int32_t nd = (int32_t)dnode.size();
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t pods_b = up(sizeof(kg_pod_dev) * (size_t)n), zrel_b = zone_release ? up((size_t)n * 2 * KG_MAX_ZONES * 8) : 0,
+                 slot_b = any_slot ? up(4 * (size_t)n) : 0, orig_b = up(4 * (size_t)n), node_b = up(4 * (size_t)nd),
+                 first_b = up(4 * (size_t)(nd + 1)), rel_b = up((size_t)n);
+    const size_t in_b = pods_b + zrel_b + slot_b + orig_b + node_b + first_b, need = in_b + rel_b;
+    if (e->unr_bytes < need) {
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (e->unr_mem) HIP_TRY(e, hipFree(e->unr_mem));
+        e->unr_mem = nullptr;
+        e->unr_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->unr_mem, need));
+        e->unr_bytes = need;
+    }
+    if (e->unr_host_bytes < need) {
+        if (e->unr_host) HIP_TRY(e, hipHostFree(e->unr_host));
+        e->unr_host = nullptr;
+        e->unr_host_bytes = 0;
+        HIP_TRY(e, hipHostMalloc(&e->unr_host, need, hipHostMallocDefault));
+        e->unr_host_bytes = need;
+    }
+    char *h = (char *)e->unr_host, *m = (char *)e->unr_mem;
+    const size_t zrel_o = pods_b, slot_o = zrel_o + zrel_b, orig_o = slot_o + slot_b, node_o = orig_o + orig_b,
+                 first_o = node_o + node_b, rel_o = in_b;
+    for (int32_t k = 0; k < n; k++) {
+        const int32_t i = order[(size_t)k];
+        kg_pod_dev_from_row(e->cfg, pods[i], ((kg_pod_dev *)h)[k]);
+        if (zone_release)
+            memcpy(h + zrel_o + (size_t)k * 2 * KG_MAX_ZONES * 8, zone_release + (size_t)i * 2 * KG_MAX_ZONES, 2 * KG_MAX_ZONES * 8);
+        if (any_slot) ((int32_t *)(h + slot_o))[k] = rsv_slot[i] >= 0 ? e->rsv_inv[(size_t)rsv_slot[i]] : -1;
+        ((int32_t *)(h + orig_o))[k] = i;
+    }
+    memcpy(h + node_o, dnode.data(), 4 * (size_t)nd);
+    memcpy(h + first_o, first.data(), 4 * (size_t)(nd + 1));
+    HIP_TRY(e, h2d(e, m, h, in_b, e->stream));
+    UnrArgs a{};
+    a.pods = (const kg_pod_dev *)m;
+    a.zrel = zone_release ? (const int64_t *)(m + zrel_o) : nullptr;
+    a.slot = any_slot ? (const int32_t *)(m + slot_o) : nullptr;
+    a.orig = (const int32_t *)(m + orig_o);
+    a.node = (const int32_t *)(m + node_o);
+    a.first = (const int32_t *)(m + first_o);
+    a.released = (uint8_t *)(m + rel_o);
+    a.n = n;
+    a.nd = nd;
+    a.n_nodes = (int32_t)e->n_nodes;
+    a.n_rsv = e->n_rsv;
+    const RsvArgs ra = rsv_args(e);
+    HIP_TRY(e, hipMemsetAsync(a.released, 0, (size_t)n, e->stream));
+    hipLaunchKernelGGL(k_unreserve, dim3((unsigned)nd), dim3(64), 0, e->stream, e->consts, e->pl, ra, a);
+    HIP_TRY(e, hipGetLastError());
+    if (any_quota && ra.quota && e->n_quota > 0) {
+        hipLaunchKernelGGL(k_unreserve_quota, dim3(1), dim3(64), 0, e->stream, ra.quota, e->n_quota, a);
+        HIP_TRY(e, hipGetLastError());
+    }
+    HIP_TRY(e, hipMemcpyAsync(h + rel_o, a.released, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the pinned block is free for the next call)
+    memcpy(released, h + rel_o, (size_t)n);
+    bool any = false;
+    for (int32_t i = 0; i < n && !any; i++) any = released[i] != 0;
+    if (any) {
+        e->slow_valid = false;   // a release can bring a node back inside the fp64 bounds (or take it out)
+        e->generation++;
+    }
     return bounds_verdict(e);
 }
 

@@ -718,6 +718,33 @@ kg_status kg_row_commit(const kg_config *cfg, kg_node_row *node, const kg_pod_ro
     return KG_OK;
 }
 
+kg_status kg_row_unreserve(const kg_config *cfg, kg_node_row *node, const kg_pod_row *pod, const int64_t *zone_release) {
+    if (!cfg || !node || !pod) return KG_ERR_INVALID_ARG;
+    if (zone_release && (!(cfg->enabled_plugins & KG_PLUGIN_NUMA) || !kg_zone_release_ok(zone_release, node->n_zones)))
+        return KG_ERR_INVALID_ARG;
+    if (!(node->flags & KG_NODE_VALID) || node->pod_count < 1) return KG_ERR_STATE;
+    kg_pod_dev pd;
+    kg_pod_dev_from_row(*cfg, *pod, pd);
+    kg_apply_unreserve(*node, pd);
+    if (zone_release) kg_zone_release(*node, zone_release);
+    return KG_OK;
+}
+
+kg_status kg_row_numa_alloc(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *pod, int64_t *zone_alloc) {
+    if (!cfg || !node || !pod || !zone_alloc) return KG_ERR_INVALID_ARG;
+    bool answered;
+    if (row_binds(*cfg, *node, *pod, answered)) return KG_ERR_UNSUPPORTED;   // the cpuset Reserve: kg_row_reserve
+    kg_pod_dev pd;
+    kg_pod_dev_from_row(*cfg, *pod, pd);
+    kg_consts k;
+    kg_consts_from_config(*cfg, k);
+    kg_node_row after = *node;   // kg_numa_commit only adds its kg_numa_out to the zones: the record is the difference
+    kg_numa_commit(k, after, pd);
+    for (int z = 0; z < KG_MAX_ZONES; z++)
+        for (int r = 0; r < 2; r++) zone_alloc[2 * z + r] = after.zone_allocated[z][r] - node->zone_allocated[z][r];
+    return KG_OK;
+}
+
 kg_status kg_row_reserve(const kg_config *cfg, kg_node_row *node, const kg_pod_row *pod, kg_cpu_info *cpus,
                          int32_t n_cpus, int32_t max_ref_count, int32_t numa_allocate_strategy, uint8_t *taken) {
     if (!cfg || !node || !pod || n_cpus < 0 || n_cpus > KG_MAX_NODE_CPUS || (n_cpus > 0 && (!cpus || !taken)) ||
@@ -934,6 +961,16 @@ void kg_pod_dev_from_row(const kg_config &c, const kg_pod_row &row, kg_pod_dev &
     d.quota = (c.enabled_plugins & KG_PLUGIN_ELASTICQUOTA) ? row.quota : -1;
     d.elig = (uint32_t)row.elig_class;
     if ((c.enabled_plugins & KG_PLUGIN_RESERVATION) && row.rsv_affinity_class >= 0) d.flags |= KGP_RSV_REQUIRED;
+}
+
+// zone_release of one entry ([KG_MAX_ZONES][2]) against the node's zone count: no negative amount, nothing past n_zones
+bool kg_zone_release_ok(const int64_t *rel, int32_t n_zones) {
+    for (int z = 0; z < KG_MAX_ZONES; z++)
+        for (int r = 0; r < 2; r++) {
+            const int64_t d = rel[2 * z + r];
+            if (d < 0 || (d != 0 && z >= n_zones)) return false;
+        }
+    return true;
 }
 
 int kg_numa_list_count(const kg_pod_row &row) {

@@ -7,6 +7,8 @@ const char *kg_res_name(const kg_config &c, int r);   // the resource-name key o
 void kg_res_sorted_order(const kg_config &c, int8_t out[KG_NUM_RES]);
 void kg_pod_dev_from_row(const kg_config &c, const kg_pod_row &row, kg_pod_dev &d);
 bool kg_pod_row_in_bounds(const kg_pod_row &row);
+// one entry's zone_release ([KG_MAX_ZONES][2]) against the node's zone count (kg_row_unreserve, kg_unreserve)
+bool kg_zone_release_ok(const int64_t *rel, int32_t n_zones);
 int kg_numa_list_count(const kg_pod_row &row);   // NodeNUMAResource hint lists the pod can produce
 // Fills the S-slot hot row (slot s ↔ resource slot_res[s]) and returns the pod's resources that
 // need a slot (compared or scored), so the caller can check the profile covers them.

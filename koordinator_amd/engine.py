@@ -41,6 +41,23 @@ def row_commit(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray) -> No
     _check(nat.lib().kg_row_commit(nat.ptr(cfg), nat.ptr(node_row), nat.ptr(pod_row)), what="kg_row_commit")
 
 
+def row_unreserve(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray, zone_release=None) -> None:
+    """kg_row_unreserve: the inverse of row_commit on a host row (in place).  `zone_release`: the pod's recorded zone
+    allocation, int64 [MAX_ZONES][2] by zone slot (row_numa_alloc at Reserve time), or None."""
+    zr = None if zone_release is None else np.ascontiguousarray(zone_release, dtype=np.int64).reshape(nat.MAX_ZONES, 2)
+    _check(nat.lib().kg_row_unreserve(nat.ptr(cfg), nat.ptr(node_row), nat.ptr(pod_row), nat.ptr(zr)),
+           what="kg_row_unreserve")
+
+
+def row_numa_alloc(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray) -> np.ndarray:
+    """kg_row_numa_alloc: the zone amounts row_commit would record for the pod on this (pre-Reserve) row, int64
+    [MAX_ZONES][2] by zone slot; all zero where the commit records nothing.  The row is not modified."""
+    out = np.zeros((nat.MAX_ZONES, 2), dtype=np.int64)
+    _check(nat.lib().kg_row_numa_alloc(nat.ptr(cfg), nat.ptr(node_row), nat.ptr(pod_row), nat.ptr(out)),
+           what="kg_row_numa_alloc")
+    return out
+
+
 def row_reserve(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray, cpus: np.ndarray, max_ref_count: int = 1,
                 numa_allocate_strategy: int = 0):
     """kg_row_reserve: the Reserve of one pair on a host row and the node's CPU_INFO array (both updated in
@@ -454,6 +471,25 @@ class Engine:
             return False
         _check(st, self, "kg_commit")
         return True
+
+    def unreserve(self, pod_rows: np.ndarray, nodes, zone_release=None, rsv_slot=None) -> np.ndarray:
+        """kg_unreserve: entry i undoes the Reserve of pod_rows[i] on nodes[i] (at most nat.UNRESERVE_MAX entries; the
+        rows travel with the call, the batch of set_pods is not touched).  `zone_release`: int64 [n][MAX_ZONES][2], the
+        pods' recorded zone allocations (row_numa_alloc), or None; `rsv_slot`: int32 [n], the set_reservations index
+        each Reserve nominated (row_eval_rsv) or -1, or None.  Returns bool [n]: the entries released (a node is
+        all-or-nothing: a removed node, one that holds fewer pods than the call releases, or an invalid slot)."""
+        rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+        n = len(rows)
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        if len(nd) != n:
+            raise ValueError("unreserve takes one node per pod row")
+        zr = None if zone_release is None else np.ascontiguousarray(zone_release, dtype=np.int64).reshape(n, nat.MAX_ZONES, 2)
+        sl = None if rsv_slot is None else np.ascontiguousarray(rsv_slot, dtype=np.int32).reshape(n)
+        out = np.zeros(n, dtype=np.uint8)
+        _check(nat.lib().kg_unreserve(self._h, nat.ptr(rows) if n else None, nat.ptr(nd) if n else None, n, 0,
+                                      nat.ptr(zr) if n else None, nat.ptr(sl) if n else None,
+                                      nat.ptr(out) if n else None), self, "kg_unreserve")
+        return out.astype(bool)
 
     def cycle_one(self, pod_row: np.ndarray, now_ns: int, commit: bool = True, planes: bool = False) -> dict:
         """kg_cycle_one: the scheduling cycle of one pod (Filter + Score over the shard, selectHost and, with
