@@ -37,6 +37,9 @@
  *                           core/group_quota_manager.go:799-805), and NodeInfo.RemovePod of ForgetPod
  *   kg_cycle_one            one pass of upstream scheduleOne for one pod in one launch: Filter + Score over every
  *                           node, selectHost, and (KG_CYCLE_COMMIT) the Reserve of the chosen node
+ *   kg_candidates           upstream numFeasibleNodesToFind + prioritizeNodes over the engine's plugins: per pod the K
+ *   / kg_candidates_merge   best feasible nodes of ALL nodes (not of a sampled subset) with each engine plugin's score,
+ *                           the hand-over to a framework that adds Score plugins of its own
  *   kg_rsv_set              reservation cache feed (reservation/cache.go:249-269 forEachAvailableReservationOnNode,
  *                           frameworkext/reservation_info.go:200-300): per-node reservation slots for the
  *                           Reservation plugin's restore / Filter / Score / Reserve (reservation/transformer.go:49-291,
@@ -981,6 +984,59 @@ kg_status kg_row_why(const kg_config *cfg, const kg_node_row *node, const kg_pod
 #define KG_DIAG_MAX_PODS 256
 kg_status kg_diagnose(kg_engine *eng, const kg_pod_row *pods, int32_t n, int64_t now_ns, uint32_t flags,
                       uint32_t *counts, uint32_t *pod_why, uint32_t *why, int32_t out_on_device);
+
+/* The k best feasible nodes of up to KG_CAND_MAX_PODS pods over every node of the shard (kg_set_shard) in one call,
+ * with the score of each engine plugin: what a profile with Score plugins outside the engine needs instead of whole
+ * planes (upstream numFeasibleNodesToFind + prioritizeNodes, but over 100 % of the nodes).  The pod rows travel with
+ * the call (as kg_diagnose and kg_cycle_one); the batch uploaded with kg_pods_set is neither read nor replaced.  The
+ * snapshot is read as it is now and nothing is mutated: generation, rows, quota state and kg_counters.placed /
+ * resolved stay.  Node indices in the keys are global.
+ *   keys       [n][k] uint64 (required): keys[p][j] is the (j + 1)-th best feasible node of pod p in
+ *              kg_eval_out.top1's encoding, (total + 1) << 32 | (0xFFFFFFFF - node), total = sum of weight * score
+ *              of the enabled engine plugins.  A list is strictly descending as uint64 (higher total first, among
+ *              equal totals the lower node index first); entries at and past the pod's feasible count are 0.
+ *   scores     [n][k][4] uint8 (may be NULL): {NodeResourcesFit, LoadAware, NodeNUMAResource, 0} scores (0..100) of
+ *              the pair, 0 for a disabled plugin; all four bytes 0 where the key is 0.
+ *   n_feasible [n] uint32 (may be NULL): the pod's feasible nodes in the shard.
+ * Defining property: with the same rows on the same engine state loaded as a batch (kg_pods_set + kg_eval, no
+ * reservation slots loaded), keys[p][0] == top1[p], the listed nodes are exactly the k largest keys formed from
+ * mask / scores / numa_scores, and n_feasible[p] is the popcount of the pod's mask row - including everything
+ * kg_eval folds into the mask: removed nodes, eligibility classes (elig_class) and the node-independent gates (a pod
+ * that fails the ElasticQuota PreFilter against the device quota state, or requires a reservation with none loaded,
+ * gets all-zero keys and n_feasible = 0).  Nodes outside the fp64 fast-path bounds are listed like any other (the
+ * exact int64 pair path).  Totals stay within the tile-key width of the placement chunks (kg_config_validate's
+ * weight limits).
+ * Every cell of [n][k], [n][k][4] and [n] is written whatever the buffers held, nothing outside them, and a NULL
+ * plane is not touched.  out_on_device != 0: the three pointers are device pointers on the engine's device (keys
+ * 8-byte aligned, the others 4-byte aligned).  The call returns after the launches completed either way.  An empty
+ * shard writes all-zero outputs and launches nothing; n = 0 is a no-op.
+ * Exact integers, identical from run to run: per-(pod, tile) descending lists, then a k-way merge; no atomics, no
+ * floating-point or order-dependent reduction.
+ * Counters: eval_calls + 1, evals + n * (E - B), out_bytes by the bytes of the planes asked for, h2d_bytes by what
+ * was uploaded.
+ * Errors (nothing launched, nothing changed, counters untouched): KG_ERR_INVALID_ARG for flags != 0, n < 0 or a null
+ * pods / keys with n > 0; KG_ERR_RANGE for k < 1, k > KG_CAND_MAX_K, n > KG_CAND_MAX_PODS, a row outside the engine
+ * bounds or an elig_class outside the loaded classes; KG_ERR_STATE without a snapshot, on a stale engine, or for a
+ * quota index without a kg_quota_set group; KG_ERR_UNSUPPORTED exactly where kg_diagnose refuses: Reservation
+ * enabled with slots loaded, under NodeNUMAResource a pod with KG_POD_NUMA_CPU_BIND or a snapshot holding a node
+ * with a CPU bind policy, and a pod with more than two NUMA hint lists.  KG_ERR_HIP when the engine-owned list
+ * buffer ([n][tiles of the shard][k + 1] uint32) cannot be allocated; the engine stays usable. */
+#define KG_CAND_MAX_K 64
+#define KG_CAND_MAX_PODS 256
+kg_status kg_candidates(kg_engine *eng, const kg_pod_row *pods, int32_t n, int64_t now_ns, int32_t k, uint32_t flags,
+                        uint64_t *keys        /* [n][k], required */,
+                        uint8_t  *scores      /* [n][k][4] = {fit, loadaware, numa, 0}; may be NULL */,
+                        uint32_t *n_feasible  /* [n]; may be NULL */,
+                        int32_t out_on_device);
+
+/* The lists that several ranks or shards returned for the same n pods, combined on the host (no engine):
+ * keys [n_lists][n][k], scores [n_lists][n][k][4] (may be NULL, then out_scores must be NULL too, and the reverse).
+ * out_keys[p] is the k largest keys of the union, descending and zero-padded; out_scores follows its keys.
+ * KG_ERR_INVALID_ARG, outputs untouched: n_lists < 1, n < 0, k outside 1..KG_CAND_MAX_K, null pointers, an input
+ * list that is not strictly descending up to its first 0 or holds a non-zero key after a 0, or a non-zero key that
+ * appears in two lists of one pod (the shards overlap). */
+kg_status kg_candidates_merge(const uint64_t *keys, const uint8_t *scores /* may be NULL */, int32_t n_lists,
+                              int32_t n, int32_t k, uint64_t *out_keys, uint8_t *out_scores /* NULL iff scores NULL */);
 
 /* Measurement: when on, every k_eval launch (kg_eval, kg_place_chunk_eval) is bracketed by a
  * pair of HIP events on the engine stream (ring of 256).  kg_eval_kernel_times writes the

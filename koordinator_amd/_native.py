@@ -67,6 +67,8 @@ DIAG_FIRST_FAIL = 0x1
 WHY_SLOTS, WHY_SLOT_REJECTED, WHY_SLOT_FEASIBLE = 32, 30, 31
 DIAG_MAX_PODS = 256
 UNRESERVE_MAX = 4096   # KG_UNRESERVE_MAX: entries of one kg_unreserve call
+CAND_MAX_K = 64          # KG_CAND_MAX_K: longest kg_candidates list
+CAND_MAX_PODS = 256      # KG_CAND_MAX_PODS: pods of one kg_candidates call
 NODE_VALID, NODE_HAS_METRIC, NODE_HAS_UPDATE_TIME, NODE_LA_PASS_NONPROD, NODE_LA_PASS_PROD = 0x1, 0x2, 0x4, 0x8, 0x10
 NODE_NUMA_OPTIONS, NODE_NUMA_TOPO_VALID, NODE_NUMA_TOPO_INVALID = 0x40, 0x80, 0x100
 
@@ -252,6 +254,7 @@ EXPORTED = [
     "kg_place_sharded", "kg_counters_get", "kg_counters_reset", "kg_comm_init_loopback", "kg_comm_kind",
     "kg_cycle_one", "kg_batch_slot_map", "kg_pods_spill_count", "kg_elig_set", "kg_elig_update",
     "kg_pods_restricted_count", "kg_row_why", "kg_diagnose", "kg_row_unreserve", "kg_row_numa_alloc", "kg_unreserve",
+    "kg_candidates", "kg_candidates_merge",
 ]
 
 _lib = None
@@ -310,6 +313,8 @@ def lib() -> ctypes.CDLL:
         "kg_diagnose": (i32, [vp, vp, i32, i64, ctypes.c_uint32, vp, vp, vp, i32]),
         "kg_row_unreserve": (i32, [vp, vp, vp, vp]), "kg_row_numa_alloc": (i32, [vp, vp, vp, vp]),
         "kg_unreserve": (i32, [vp, vp, vp, i32, ctypes.c_uint32, vp, vp, vp]),
+        "kg_candidates": (i32, [vp, vp, i32, i64, i32, ctypes.c_uint32, vp, vp, vp, i32]),
+        "kg_candidates_merge": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if host_only and not hasattr(L, name):

@@ -86,6 +86,8 @@
 //   119-124 k_unreserve               node group, node (row and planes), entry range, reservation node, slot range,
 //                                     released (call index)
 //   125-126 k_unreserve_quota         released (call index, read), quota group of a chain
+//   127-128 k_cand                    pod row (read; k_cand_merge too), per-(pod, tile) lists and counts
+//   129-132 k_cand_merge              per-(pod, tile) lists and counts (read), keys, scores, n_feasible
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -3729,6 +3731,211 @@ __global__ __launch_bounds__(64) void k_why_reduce(kg_consts c, const uint32_t *
 }
 
 // ---------------------------------------------------------------------------------------
+// kg_candidates: the k best feasible nodes of listed pods over the shard, with the engine plugins' scores
+// ---------------------------------------------------------------------------------------
+struct CandArgs {
+    int64_t node_end;            // the shard's end
+    int64_t now_ns;
+    int32_t tile_begin, shard_tiles;
+    int32_t n_groups, pods_per_group;
+    int32_t n_pods;
+    int32_t k;                   // 1..KG_CAND_MAX_K
+};
+
+// tile_topk for a wave-uniform k ≤ 64: the k best of one pod's 1024 tile keys in descending order, lane r keeps the
+// r-th (0 where the tile has fewer feasible nodes); `count`: the tile's non-zero keys (wave-uniform)
+__device__ __forceinline__ uint32_t tile_topk_n(const uint32_t *keys, int k, uint32_t &count) {
+    const int lane = threadIdx.x & 63;
+    uint32_t v[KG_TILE / 64];
+    uint32_t cnt = 0u;
+#pragma unroll
+    for (int i = 0; i < KG_TILE / 64; i++) {
+        v[i] = keys[lane + 64 * i];
+        cnt += (uint32_t)__popcll(__ballot(v[i] != 0u));
+    }
+    count = cnt;
+    uint32_t out = 0;
+    for (int r = 0; r < k; r++) {
+        uint32_t m = v[0];
+#pragma unroll
+        for (int i = 1; i < KG_TILE / 64; i++) m = m > v[i] ? m : v[i];
+        m = wave_max_u32(m);
+        if (m == 0) break;   // wave-uniform
+        out = lane == r ? m : out;
+#pragma unroll
+        for (int i = 0; i < KG_TILE / 64; i++) v[i] = v[i] == m ? 0u : v[i];
+    }
+    return out;
+}
+
+// k_why's geometry: one workgroup = one 1024-node tile × a group of the pods (XCD-aware order), two nodes per lane,
+// the tile's node registers loaded once, pod rows staged KG_SPILL_CHUNK at a time in LDS.  Per pair the generic pair
+// path of k_cycle_one (eval_pair, then kg_numa_eval_any for a feasible pair under NodeNUMAResource); the pair's
+// 32-bit tile key goes into the LDS key buffer of k_eval_spill<…, TOPK> (8 pods × 1024 keys).  Unlike a placement
+// chunk the nodes outside the fp64 bounds are listed: eval_pair answers them on the exact path, and nobody re-scores
+// a slow list behind this kernel.  Then a wave per pod takes the tile's k best keys (tile_topk_n) and stores the
+// descending list and the tile's feasible count into `slab` [n][shard_tiles][k + 1] with plain stores, every slot
+// of it: no atomics, the merge below reads only what this launch wrote.
+template <bool NUMA>
+__global__ __launch_bounds__(KG_BLOCK) void k_cand(kg_consts c, kg_planes pl, CandArgs a,
+                                                   const kg_pod_dev *__restrict__ pods, uint32_t *__restrict__ slab) {
+    __shared__ __attribute__((aligned(16))) kg_pod_dev lp[KG_SPILL_CHUNK];
+    __shared__ __attribute__((aligned(16))) uint32_t kbuf[KG_SPILL_CHUNK * KG_BLOCK * 2];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x, xcd = b % KG_XCDS, r = b / KG_XCDS;
+    const int tile_rel = (r / a.n_groups) * KG_XCDS + xcd, group = r % a.n_groups;
+    if (tile_rel >= a.shard_tiles) return;   // grid padded to a multiple of 8 tiles; block-uniform
+    const int tile = a.tile_begin + tile_rel;
+    const int64_t wave_base = (int64_t)tile * KG_TILE + wave * 128;
+    const int64_t node0 = wave_base + lane, node1 = node0 + 64;
+    const bool in0 = node0 < a.node_end, in1 = node1 < a.node_end;
+    const BatchMasks bm{0xFFu, 0xFFu};
+    NodeRegs n0, n1;
+    load_node(c, pl, node0, in0, bm, a.now_ns, n0);
+    load_node(c, pl, node1, in1, bm, a.now_ns, n1);
+    // key = ((tot + 1) << 10) | (1023 − local node) ⇒ max = best total, then lowest node
+    const uint32_t local0 = (uint32_t)(wave * 128 + lane);
+    const uint32_t kb0 = (1u << KG_TILE_SHIFT) + (KG_TILE - 1) - local0, kb1 = kb0 - 64;
+    constexpr int POD_DW = (int)(sizeof(kg_pod_dev) / 4);
+    const int k1 = a.k + 1;
+    const int gb = group * a.pods_per_group;
+    const int ge = min(gb + a.pods_per_group, a.n_pods);
+    for (int q0 = gb; q0 < ge; q0 += KG_SPILL_CHUNK) {
+        const int nq = min(KG_SPILL_CHUNK, ge - q0);
+        for (int i = tid; i < nq * POD_DW; i += KG_BLOCK) {
+            const int j = i / POD_DW, w = i - j * POD_DW;
+            reinterpret_cast<uint32_t *>(&lp[j])[w] =
+                KG_IN(127, q0 + j, a.n_pods) ? reinterpret_cast<const uint32_t *>(pods + q0 + j)[w] : 0u;
+        }
+        __syncthreads();
+        for (int j = 0; j < nq; j++) {
+            uint32_t fit0 = 0, la0 = 0, numa0 = 0, fit1 = 0, la1 = 0, numa1 = 0;
+            bool ok0 = in0 && eval_pair(c, pl, lp[j], n0, node0, a.now_ns, fit0, la0);
+            bool ok1 = in1 && eval_pair(c, pl, lp[j], n1, node1, a.now_ns, fit1, la1);
+            if constexpr (NUMA) {
+                if (ok0) {
+                    const uint64_t ns = kg_numa_eval_any(c, pl.rows[node0], lp[j]);
+                    ok0 = (ns >> 32) != 0;
+                    numa0 = (uint32_t)ns;
+                }
+                if (ok1) {
+                    const uint64_t ns = kg_numa_eval_any(c, pl.rows[node1], lp[j]);
+                    ok1 = (ns >> 32) != 0;
+                    numa1 = (uint32_t)ns;
+                }
+            }
+            kbuf[j * 2 * KG_BLOCK + tid] = ok0 ? (total_of(c, fit0, la0, numa0) << KG_TILE_SHIFT) + kb0 : 0u;
+            kbuf[j * 2 * KG_BLOCK + KG_BLOCK + tid] = ok1 ? (total_of(c, fit1, la1, numa1) << KG_TILE_SHIFT) + kb1 : 0u;
+        }
+        __syncthreads();
+        for (int j = wave; j < nq; j += KG_BLOCK / 64) {   // a wave per pod
+            const int p = q0 + j;
+            uint32_t cnt;
+            const uint32_t t = tile_topk_n(kbuf + j * 2 * KG_BLOCK, a.k, cnt);
+            if (KG_IN2(128, p, a.n_pods, tile_rel, a.shard_tiles)) {
+                uint32_t *d = slab + ((int64_t)p * a.shard_tiles + tile_rel) * k1;
+                if (lane < a.k) d[lane] = t;
+                if (lane == 0) d[a.k] = cnt;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// a tile key of tile `tile` as a kg_eval_out.top1 key: (total + 1) << 32 | (0xFFFFFFFF − node); 0 stays 0
+__device__ __forceinline__ unsigned long long cand_widen(uint32_t tk, int tile) {
+    if (!tk) return 0ull;
+    const unsigned long long node = (unsigned long long)tile * KG_TILE + ((KG_TILE - 1) - (tk & (KG_TILE - 1)));
+    return ((unsigned long long)(tk >> KG_TILE_SHIFT) << 32) | (0xFFFFFFFFull - node);
+}
+
+// The merge of a pod's tile lists: one wave per pod.  Lane l owns tiles l, l + 64, … and keeps, in LDS cells only it
+// touches, each tile's head index and head key; the lists are descending, so the pod's best remaining key is some
+// tile's head.  k rounds: a 64-bit wave max over the lanes' best heads (widened to global keys: unique, they carry
+// the node), lane r keeps round r's key, the owner advances that tile.  The tile counts are summed for n_feasible.
+// Lane r then evaluates its one pair again (load_node, eval_pair, NodeNUMAResource) for the plugin scores.  A pod
+// that fails a node-independent gate (kg_pod_why: ElasticQuota's PreFilter, a required reservation with none
+// loaded) gets zeros, as kg_eval folds the gate into its mask.  Every cell of the pod's outputs is written.
+template <bool NUMA>
+__global__ __launch_bounds__(64) void k_cand_merge(kg_consts c, kg_planes pl, CandArgs a,
+                                                   const kg_pod_dev *__restrict__ pods, const uint32_t *__restrict__ slab,
+                                                   const kg_quota *__restrict__ quota, int32_t n_quota,
+                                                   int32_t check_parent, int32_t rsv_slots,
+                                                   unsigned long long *__restrict__ keys, uint32_t *__restrict__ scores,
+                                                   uint32_t *__restrict__ n_feasible) {
+    __shared__ __attribute__((aligned(16))) kg_pod_dev lp;
+    __shared__ uint32_t hkey[KG_MAX_TILES];
+    __shared__ uint8_t hidx[KG_MAX_TILES];
+    const int p = blockIdx.x;
+    if (p >= a.n_pods) return;   // block-uniform
+    const int lane = threadIdx.x;
+    constexpr int POD_DW = (int)(sizeof(kg_pod_dev) / 4);
+    for (int i = lane; i < POD_DW; i += 64)
+        reinterpret_cast<uint32_t *>(&lp)[i] = KG_IN(127, p, a.n_pods) ? reinterpret_cast<const uint32_t *>(pods + p)[i] : 0u;
+    __syncthreads();
+    const int k1 = a.k + 1, tiles = min(a.shard_tiles, KG_MAX_TILES);
+    const uint32_t *src = slab + (int64_t)p * a.shard_tiles * k1;
+    unsigned long long best = 0ull;   // the best head of this lane's tiles
+    int best_t = -1;
+    uint32_t cnt = 0u;
+    for (int t = lane; t < tiles; t += 64) {
+        uint32_t h = 0u;
+        if (KG_IN2(129, p, a.n_pods, t, a.shard_tiles)) {
+            h = src[(int64_t)t * k1];
+            cnt += src[(int64_t)t * k1 + a.k];
+        }
+        hkey[t] = h;
+        hidx[t] = 0;
+        const unsigned long long g = cand_widen(h, a.tile_begin + t);
+        if (g > best) {
+            best = g;
+            best_t = t;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    unsigned long long mine = 0ull;
+    for (int r = 0; r < a.k; r++) {
+        const unsigned long long m = wave_max_u64(best);
+        if (m == 0ull) break;   // wave-uniform
+        mine = lane == r ? m : mine;
+        if (best == m) {   // the one owner: its tile's next entry, then its best head again
+            const int h = hidx[best_t] + 1;
+            hidx[best_t] = (uint8_t)h;
+            hkey[best_t] = (h < a.k && KG_IN2(129, p, a.n_pods, best_t, a.shard_tiles)) ? src[(int64_t)best_t * k1 + h] : 0u;
+            best = 0ull;
+            best_t = -1;
+            for (int t = lane; t < tiles; t += 64) {
+                const unsigned long long g = cand_widen(hkey[t], a.tile_begin + t);
+                if (g > best) {
+                    best = g;
+                    best_t = t;
+                }
+            }
+        }
+    }
+    const bool gated = kg_pod_why(c, quota, n_quota, check_parent, rsv_slots != 0, lp) != 0u;
+    if (gated) mine = 0ull;
+    uint32_t sc = 0u;
+    const int64_t node = (int64_t)(0xFFFFFFFFull - (mine & 0xFFFFFFFFull));
+    if (scores && mine && node < a.node_end) {   // (a listed node lies in the shard: k_cand wrote the key)
+        const BatchMasks bm{0xFFu, 0xFFu};
+        NodeRegs n;
+        load_node(c, pl, node, true, bm, a.now_ns, n);
+        uint32_t fit = 0, la = 0, numa = 0;
+        (void)eval_pair(c, pl, lp, n, node, a.now_ns, fit, la);
+        if constexpr (NUMA) numa = (uint32_t)kg_numa_eval_any(c, pl.rows[node], lp);
+        sc = fit | (la << 8) | (numa << 16);
+    }
+    if (lane < a.k) {
+        if (KG_IN2(130, p, a.n_pods, lane, a.k)) keys[(int64_t)p * a.k + lane] = mine;
+        if (scores && KG_IN2(131, p, a.n_pods, lane, a.k)) scores[(int64_t)p * a.k + lane] = sc;
+    }
+    if (n_feasible && lane == 0 && KG_IN(132, p, a.n_pods)) n_feasible[p] = gated ? 0u : cnt;
+}
+
+// ---------------------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------------------
 struct kg_engine {
@@ -3883,6 +4090,11 @@ struct kg_engine {
     void *diag_mem = nullptr;
     size_t diag_bytes = 0;
     void *diag_host = nullptr;
+    // kg_candidates: the call's pod rows, staged outputs and per-(pod, tile) lists on the device (one buffer, grown on
+    // demand) and the pinned host block its pod rows pass through
+    void *cand_mem = nullptr;
+    size_t cand_bytes = 0;
+    void *cand_host = nullptr;
     // kg_unreserve: the call's grouped entries on the device and the pinned block they pass through (both grown on
     // demand), the zone count of every node's row (host mirror of kg_node_row.n_zones, which no commit changes: the
     // zone arguments are validated before anything is launched) and the caller index → device slot map of kg_rsv_set
@@ -4917,6 +5129,8 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->cyc_out) (void)hipHostFree(e->cyc_out);
     if (e->diag_mem) (void)hipFree(e->diag_mem);
     if (e->diag_host) (void)hipHostFree(e->diag_host);
+    if (e->cand_mem) (void)hipFree(e->cand_mem);
+    if (e->cand_host) (void)hipHostFree(e->cand_host);
     if (e->unr_mem) (void)hipFree(e->unr_mem);
     if (e->unr_host) (void)hipHostFree(e->unr_host);
     if (e->hot_lax) (void)hipFree(e->hot_lax);
@@ -6841,6 +7055,127 @@ kg_status kg_diagnose(kg_engine *e, const kg_pod_row *pods, int32_t n, int64_t n
         HIP_TRY(e, hipMemcpyAsync(counts, cnt_d, cnt_b, hipMemcpyDeviceToHost, e->stream));
         if (pod_why) HIP_TRY(e, hipMemcpyAsync(pod_why, pw_d, pw_b, hipMemcpyDeviceToHost, e->stream));
         if (why) HIP_TRY(e, hipMemcpyAsync(why, why_d, why_b, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the pinned pod rows are free for the next call)
+    return bounds_verdict(e);
+}
+
+// The k best feasible nodes of n pods over the shard: k_cand (per-(pod, tile) descending lists and feasible counts)
+// and k_cand_merge (the k-way merge, the plugin scores of the listed pairs, the pod-level gates), then one stream
+// synchronisation.  Like kg_diagnose the pod rows travel with the call and nothing of the engine's state is touched.
+kg_status kg_candidates(kg_engine *e, const kg_pod_row *pods, int32_t n, int64_t now_ns, int32_t k, uint32_t flags,
+                        uint64_t *keys, uint8_t *scores, uint32_t *n_feasible, int32_t out_on_device) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (flags != 0) return set_err(e, KG_ERR_INVALID_ARG, "unknown kg_candidates flags 0x%x", flags);
+    if (n < 0 || (n > 0 && (!pods || !keys))) return set_err(e, KG_ERR_INVALID_ARG, "null pods or keys");
+    if (k < 1 || k > KG_CAND_MAX_K) return set_err(e, KG_ERR_RANGE, "kg_candidates takes k in 1..%d (got %d)", KG_CAND_MAX_K, k);
+    if (n > KG_CAND_MAX_PODS) return set_err(e, KG_ERR_RANGE, "kg_candidates takes at most %d pods (got %d)", KG_CAND_MAX_PODS, n);
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised");
+    const uint32_t plug = e->cfg.enabled_plugins;
+    const bool numa_on = (plug & KG_PLUGIN_NUMA) != 0;
+    for (int32_t i = 0; i < n; i++) {
+        const kg_pod_row &pod = pods[i];
+        if (!kg_pod_row_in_bounds(pod)) return set_err(e, KG_ERR_RANGE, "pod %d: request outside the engine bounds", i);
+        if (pod.elig_class < 0 || pod.elig_class > e->pl.elig_classes)
+            return set_err(e, KG_ERR_RANGE, "pod %d: elig_class %d outside the loaded eligibility classes (have %d: kg_elig_set)",
+                           i, pod.elig_class, e->pl.elig_classes);
+    }
+    // what the per-pair path does not answer (kg_diagnose's list)
+    if ((plug & KG_PLUGIN_RESERVATION) && e->n_rn > 0)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_candidates with reservation slots loaded (the restore changes NodeInfo per pair)");
+    if (numa_on && e->n_node_bind_nodes > 0)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_candidates does not answer cpuset binding (a node with a CPU bind policy)");
+    for (int32_t i = 0; i < n; i++) {
+        const kg_pod_row &pod = pods[i];
+        const bool numa_pod = numa_on && !(pod.flags & KG_POD_NUMA_SKIP);
+        if (numa_pod && (pod.flags & KG_POD_NUMA_CPU_BIND))
+            return set_err(e, KG_ERR_UNSUPPORTED, "pod %d: kg_candidates does not answer cpuset binding", i);
+        if (numa_pod && kg_numa_list_count(pod) > KG_NUMA_MAX_LISTS)
+            return set_err(e, KG_ERR_UNSUPPORTED, "pod %d: more than %d NUMA hint lists", i, KG_NUMA_MAX_LISTS);
+        if ((plug & KG_PLUGIN_ELASTICQUOTA) && pod.quota >= e->n_quota)
+            return set_err(e, KG_ERR_STATE, "pod %d: quota index %d without a kg_quota_set group (have %d)", i, pod.quota,
+                           e->n_quota);
+    }
+    if (n == 0) return KG_OK;
+    const bool dev = out_on_device != 0;
+    const int64_t width = e->shard_end - e->shard_begin;
+    const size_t key_b = (size_t)n * (size_t)k * 8, sc_b = (size_t)n * (size_t)k * 4, nf_b = (size_t)n * 4;
+    const size_t out_b = key_b + (scores ? sc_b : 0) + (n_feasible ? nf_b : 0);
+    if (width <= 0) {   // an empty shard: all-zero outputs, nothing to launch
+        if (dev) {
+            HIP_TRY(e, hipMemsetAsync(keys, 0, key_b, e->stream));
+            if (scores) HIP_TRY(e, hipMemsetAsync(scores, 0, sc_b, e->stream));
+            if (n_feasible) HIP_TRY(e, hipMemsetAsync(n_feasible, 0, nf_b, e->stream));
+            HIP_TRY(e, hipStreamSynchronize(e->stream));
+        } else {
+            memset(keys, 0, key_b);
+            if (scores) memset(scores, 0, sc_b);
+            if (n_feasible) memset(n_feasible, 0, nf_b);
+        }
+        e->ctr.eval_calls++;
+        e->ctr.out_bytes += out_b;
+        return KG_OK;
+    }
+    const int64_t tile_begin = e->shard_begin / KG_TILE;
+    const int64_t shard_tiles = (e->shard_end + KG_TILE - 1) / KG_TILE - tile_begin;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t pods_b = sizeof(kg_pod_dev) * (size_t)n;
+    const size_t slab_b = (size_t)n * (size_t)shard_tiles * (size_t)(k + 1) * 4;
+    const size_t need = up(pods_b) + up(key_b) + up(sc_b) + up(nf_b) + up(slab_b);
+    if (e->cand_bytes < need) {   // (a failed allocation leaves the engine usable: nothing was launched)
+        if (e->cand_mem) HIP_TRY(e, hipFree(e->cand_mem));
+        e->cand_mem = nullptr;
+        e->cand_bytes = 0;
+        const hipError_t hs = hipMalloc(&e->cand_mem, need);
+        if (hs != hipSuccess) {
+            (void)hipGetLastError();
+            e->cand_mem = nullptr;
+            e->err = std::string("kg_candidates: hipMalloc of ") + std::to_string(need) + " bytes: " + hipGetErrorString(hs);
+            return KG_ERR_HIP;
+        }
+        e->cand_bytes = need;
+    }
+    if (!e->cand_host) HIP_TRY(e, hipHostMalloc(&e->cand_host, sizeof(kg_pod_dev) * KG_CAND_MAX_PODS, hipHostMallocDefault));
+    e->ctr.eval_calls++;
+    e->ctr.evals += (uint64_t)n * (uint64_t)width;
+    e->ctr.out_bytes += out_b;
+    char *m = (char *)e->cand_mem;
+    kg_pod_dev *pods_d = (kg_pod_dev *)m;
+    unsigned long long *keys_d = dev ? (unsigned long long *)keys : (unsigned long long *)(m + up(pods_b));
+    uint32_t *sc_d = !scores ? nullptr : dev ? (uint32_t *)scores : (uint32_t *)(m + up(pods_b) + up(key_b));
+    uint32_t *nf_d = !n_feasible ? nullptr : dev ? n_feasible : (uint32_t *)(m + up(pods_b) + up(key_b) + up(sc_b));
+    uint32_t *slab = (uint32_t *)(m + up(pods_b) + up(key_b) + up(sc_b) + up(nf_b));
+    kg_pod_dev *pods_h = (kg_pod_dev *)e->cand_host;
+    for (int32_t i = 0; i < n; i++) kg_pod_dev_from_row(e->cfg, pods[i], pods_h[i]);
+    HIP_TRY(e, h2d(e, pods_d, pods_h, pods_b, e->stream));
+    CandArgs a{};
+    a.node_end = e->shard_end;
+    a.now_ns = now_ns;
+    a.tile_begin = (int32_t)tile_begin;
+    a.shard_tiles = (int32_t)shard_tiles;
+    // pods per workgroup as kg_diagnose: whole LDS passes, about 2048 workgroups on a large launch
+    int64_t ppg = ((int64_t)n * shard_tiles + 2047) / 2048;
+    ppg = (ppg + KG_SPILL_CHUNK - 1) / KG_SPILL_CHUNK * KG_SPILL_CHUNK;
+    if (ppg < KG_SPILL_CHUNK) ppg = KG_SPILL_CHUNK;
+    const int64_t groups = (n + ppg - 1) / ppg;
+    const int64_t blocks = (shard_tiles + KG_XCDS - 1) / KG_XCDS * KG_XCDS * groups;
+    a.n_groups = (int32_t)groups;
+    a.pods_per_group = (int32_t)ppg;
+    a.n_pods = n;
+    a.k = k;
+    hipLaunchKernelGGL(numa_on ? k_cand<true> : k_cand<false>, dim3((unsigned)blocks), dim3(KG_BLOCK), 0, e->stream,
+                       e->consts, e->pl, a, (const kg_pod_dev *)pods_d, slab);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(numa_on ? k_cand_merge<true> : k_cand_merge<false>, dim3((unsigned)n), dim3(64), 0, e->stream,
+                       e->consts, e->pl, a, (const kg_pod_dev *)pods_d, (const uint32_t *)slab,
+                       (plug & KG_PLUGIN_ELASTICQUOTA) ? (const kg_quota *)e->quota : (const kg_quota *)nullptr, e->n_quota,
+                       (int32_t)(e->cfg.eq_check_parent_quota != 0), (int32_t)(e->n_rn > 0), keys_d, sc_d, nf_d);
+    HIP_TRY(e, hipGetLastError());
+    if (!dev) {
+        HIP_TRY(e, hipMemcpyAsync(keys, keys_d, key_b, hipMemcpyDeviceToHost, e->stream));
+        if (scores) HIP_TRY(e, hipMemcpyAsync(scores, sc_d, sc_b, hipMemcpyDeviceToHost, e->stream));
+        if (n_feasible) HIP_TRY(e, hipMemcpyAsync(n_feasible, nf_d, nf_b, hipMemcpyDeviceToHost, e->stream));
     }
     HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the pinned pod rows are free for the next call)
     return bounds_verdict(e);

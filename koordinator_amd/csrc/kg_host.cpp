@@ -1087,3 +1087,40 @@ extern "C" kg_status kg_batch_slot_map(const kg_config *cfg, const kg_pod_row *p
         for (int32_t i = 0; i < n; i++) spill[i] = (need[(size_t)i] & ~(others | 0x3u)) ? 1 : 0;
     return KG_OK;
 }
+
+// kg_candidates_merge (koord_gpu.h): the candidate lists of several ranks or shards for the same pods, combined.
+// Every input is validated before the first output cell is written.
+extern "C" kg_status kg_candidates_merge(const uint64_t *keys, const uint8_t *scores, int32_t n_lists, int32_t n,
+                                         int32_t k, uint64_t *out_keys, uint8_t *out_scores) {
+    if (n_lists < 1 || n < 0 || k < 1 || k > KG_CAND_MAX_K || !keys || !out_keys || (scores == nullptr) != (out_scores == nullptr))
+        return KG_ERR_INVALID_ARG;
+    const size_t N = (size_t)n, K = (size_t)k;
+    for (size_t l = 0; l < (size_t)n_lists * N; l++) {   // each list: strictly descending up to its first 0, then zeros
+        const uint64_t *list = keys + l * K;
+        for (size_t j = 1; j < K; j++)
+            if (list[j] != 0 && list[j] >= list[j - 1]) return KG_ERR_INVALID_ARG;   // (covers a key after a 0)
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> all;   // (key, its cell l · k + j of the pod's lists)
+    std::vector<uint32_t> pick(N * K, UINT32_MAX);     // per output cell: the input cell it takes, none ⇔ UINT32_MAX
+    for (size_t p = 0; p < N; p++) {
+        all.clear();
+        for (size_t l = 0; l < (size_t)n_lists; l++)
+            for (size_t j = 0; j < K && keys[(l * N + p) * K + j] != 0; j++)
+                all.emplace_back(keys[(l * N + p) * K + j], (uint32_t)(l * K + j));
+        std::sort(all.begin(), all.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
+        for (size_t i = 1; i < all.size(); i++)
+            if (all[i].first == all[i - 1].first) return KG_ERR_INVALID_ARG;   // the same (total, node) from two lists
+        for (size_t j = 0; j < K && j < all.size(); j++) pick[p * K + j] = all[j].second;
+    }
+    for (size_t p = 0; p < N; p++)
+        for (size_t j = 0; j < K; j++) {
+            const uint32_t c = pick[p * K + j];
+            const size_t src = c == UINT32_MAX ? 0 : (((size_t)c / K) * N + p) * K + (size_t)c % K;
+            out_keys[p * K + j] = c == UINT32_MAX ? 0 : keys[src];
+            if (out_scores) {
+                if (c == UINT32_MAX) memset(out_scores + (p * K + j) * 4, 0, 4);
+                else memcpy(out_scores + (p * K + j) * 4, scores + src * 4, 4);
+            }
+        }
+    return KG_OK;
+}

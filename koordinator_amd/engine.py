@@ -577,6 +577,34 @@ class Engine:
                                      nat.DIAG_FIRST_FAIL if first_fail else 0, counts_ptr or None, pod_why_ptr or None,
                                      why_ptr or None, 1), self, "kg_diagnose")
 
+    def candidates(self, pod_rows: np.ndarray, now_ns: int, k: int, scores: bool = True) -> dict:
+        """kg_candidates: the k best feasible nodes of each pod (at most nat.CAND_MAX_PODS rows, 1 ≤ k ≤
+        nat.CAND_MAX_K; the rows travel with the call, the batch of set_pods is not touched) over the shard, in one
+        call.  Returns keys [n][k] u64 (eval()'s top1 encoding, strictly descending, 0 past the pod's feasible
+        count), nodes [n][k] i32 (−1 where none), totals [n][k] i64 (−1 where none), n_feasible [n] u32 and, with
+        `scores`, scores [n][k][4] u8 = {fit, loadaware, numa, 0}.  Mutates nothing."""
+        rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+        n, k = len(rows), int(k)
+        kk = max(k, 0)
+        res = {"keys": np.zeros((n, kk), dtype=np.uint64), "n_feasible": np.zeros(n, dtype=np.uint32)}
+        if scores:
+            res["scores"] = np.zeros((n, kk, 4), dtype=np.uint8)
+        _check(nat.lib().kg_candidates(self._h, nat.ptr(rows) if n else None, n, int(now_ns), k, 0,
+                                       nat.ptr(res["keys"]) if n else None,
+                                       nat.ptr(res["scores"]) if scores and n else None,
+                                       nat.ptr(res["n_feasible"]) if n else None, 0), self, "kg_candidates")
+        node, total = decode_top1(res["keys"])
+        res["nodes"], res["totals"] = node.astype(np.int32), total
+        return res
+
+    def candidates_device(self, pod_rows: np.ndarray, now_ns: int, k: int, keys_ptr: int, scores_ptr: int = 0,
+                          n_feasible_ptr: int = 0) -> None:
+        """kg_candidates into caller-owned device buffers (keys 8-byte aligned, the others 4-byte aligned, any
+        previous content), as diagnose_device; the call returns after the launches completed."""
+        rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+        _check(nat.lib().kg_candidates(self._h, nat.ptr(rows), len(rows), int(now_ns), int(k), 0, keys_ptr or None,
+                                       scores_ptr or None, n_feasible_ptr or None, 1), self, "kg_candidates")
+
     # Reservation / ElasticQuota -----------------------------------------------------------
     def set_reservations(self, rsv: np.ndarray) -> None:
         rsv = np.ascontiguousarray(rsv, dtype=nat.RESERVATION)
@@ -606,6 +634,27 @@ def decode_top1(keys: np.ndarray):
     node = np.where(ok, (np.uint64(0xFFFFFFFF) - (keys & np.uint64(0xFFFFFFFF))).astype(np.int64), -1)
     total = np.where(ok, (keys >> np.uint64(32)).astype(np.int64) - 1, -1)
     return node, total
+
+
+def merge_candidates(results: Sequence[dict]) -> dict:
+    """kg_candidates_merge: the candidates() results of several ranks or shards for the same pods and the same k,
+    combined on the host.  Returns keys, nodes, totals, n_feasible (the sum over the disjoint shards) and, when every
+    result carries them, scores.  Raises EngineError (KG_ERR_INVALID_ARG) for malformed or overlapping lists."""
+    if not results:
+        raise ValueError("merge_candidates takes at least one result")
+    keys = np.ascontiguousarray(np.stack([np.asarray(r["keys"], dtype=np.uint64) for r in results]))
+    _, n, k = keys.shape
+    with_scores = all("scores" in r for r in results)
+    sc = np.ascontiguousarray(np.stack([np.asarray(r["scores"], dtype=np.uint8) for r in results])) if with_scores else None
+    res = {"keys": np.zeros((n, k), dtype=np.uint64)}
+    if with_scores:
+        res["scores"] = np.zeros((n, k, 4), dtype=np.uint8)
+    _check(nat.lib().kg_candidates_merge(nat.ptr(keys), nat.ptr(sc), len(results), n, k, nat.ptr(res["keys"]),
+                                         nat.ptr(res["scores"]) if with_scores else None), what="kg_candidates_merge")
+    node, total = decode_top1(res["keys"])
+    res["nodes"], res["totals"] = node.astype(np.int32), total
+    res["n_feasible"] = np.sum([np.asarray(r["n_feasible"], dtype=np.uint32) for r in results], axis=0, dtype=np.uint32)
+    return res
 
 
 def pack_eligibility(masks: np.ndarray) -> np.ndarray:
