@@ -40,6 +40,11 @@
  *   kg_candidates           upstream numFeasibleNodesToFind + prioritizeNodes over the engine's plugins: per pod the K
  *   / kg_candidates_merge   best feasible nodes of ALL nodes (not of a sampled subset) with each engine plugin's score,
  *                           the hand-over to a framework that adds Score plugins of its own
+ *   kg_bound_set / _update  NodeInfo.Pods of every node as the preemption dry run reads it: the bound pods' requests, quota
+ *                           group, priority (corev1helpers.PodPriority) and start time (util.GetPodStartTime)
+ *   kg_preempt              ElasticQuota's PostFilter preemption (elasticquota/plugin.go:302-321): SelectVictimsOnNode
+ *   / kg_row_preempt        (preempt.go:111-215) dry-run on ALL nodes (GetOffsetAndNumCandidates, preempt.go:43-45), and
+ *   / kg_preempt_merge      upstream pickOneNodeForPreemption (k8s v1.24.15 framework/preemption/preemption.go)
  *   kg_rsv_set              reservation cache feed (reservation/cache.go:249-269 forEachAvailableReservationOnNode,
  *                           frameworkext/reservation_info.go:200-300): per-node reservation slots for the
  *                           Reservation plugin's restore / Filter / Score / Reserve (reservation/transformer.go:49-291,
@@ -1037,6 +1042,107 @@ kg_status kg_candidates(kg_engine *eng, const kg_pod_row *pods, int32_t n, int64
  * appears in two lists of one pod (the shards overlap). */
 kg_status kg_candidates_merge(const uint64_t *keys, const uint8_t *scores /* may be NULL */, int32_t n_lists,
                               int32_t n, int32_t k, uint64_t *out_keys, uint8_t *out_scores /* NULL iff scores NULL */);
+
+/* Preemption dry run: which pods would have to go, on which node, for a pod that fits nowhere (ElasticQuota's
+ * PostFilter: elasticquota/plugin.go:302-321 runs the upstream preemption evaluator over every node,
+ * preempt.go:43-45, with SelectVictimsOnNode of preempt.go:111-215).
+ *
+ * The bound-pod table is NodeInfo.Pods of every node of the snapshot (not of the shard): per node a list of at most
+ * KG_BOUND_MAX_PER_NODE pods, each a kg_pod_row plus its priority (corev1helpers.PodPriority: Spec.Priority, 0 when
+ * nil) and start time (Status.StartTime in ns; INT64_MAX for nil, where upstream takes Now(), later than every real
+ * start).  Of a row the table keeps request / request_present / nonzero_request (the deltas of NodeInfo.RemovePod /
+ * AddPodInfo), numa_request / numa_request_present (core.PodRequestsAndLimits, the quota deltas), quota and
+ * flags & KG_POD_NON_PREEMPTIBLE; kg_bound_download returns exactly those, every other field of a row zero.
+ * Position b of a pod in its node's list (the caller's order) is its identity in every output: bit b of a victim mask.
+ * The engine keeps each list in util.MoreImportantPod order - higher priority first, then the earlier start; ties keep
+ * the caller's order (the reference's sort.Slice leaves them unspecified) - and remembers each entry's position.
+ * kg_bound_set replaces the whole table: first[n_nodes + 1] are CSR offsets into rows / priority / start_ns (first[0]
+ * = 0, non-decreasing, no list longer than max_per_node), max_per_node (1..KG_BOUND_MAX_PER_NODE) the slots the table
+ * keeps per node.  kg_bound_update replaces one node's list (n = 0 empties it).  kg_snapshot_reset drops the table;
+ * kg_snapshot_upsert / _remove leave it alone.  The engine does not check that a node row's `requested` is the sum of
+ * its list, and kg_place / kg_commit / kg_unreserve do not touch the table: the caller keeps it in step with
+ * kg_bound_update the way it keeps rows in step with kg_snapshot_upsert.
+ * Errors (nothing changed): KG_ERR_INVALID_ARG for null pointers; KG_ERR_STATE without a snapshot, and for
+ * kg_bound_update / kg_bound_download before a kg_bound_set; KG_ERR_RANGE for a node or a count out of range (n or cap
+ * above the table's max_per_node, a list longer than it), offsets that do not rise, or a row outside the engine bounds.
+ * h2d_bytes grows by what was uploaded. */
+#define KG_BOUND_MAX_PER_NODE 128
+kg_status kg_bound_set(kg_engine *eng, const int32_t *first /* [n_nodes + 1], CSR offsets */, const kg_pod_row *rows,
+                       const int32_t *priority, const int64_t *start_ns, int32_t max_per_node /* 1..128: the stride kept */);
+kg_status kg_bound_update(kg_engine *eng, int32_t node, const kg_pod_row *rows, const int32_t *priority,
+                          const int64_t *start_ns, int32_t n /* 0..max_per_node */);   /* replaces one node's list */
+kg_status kg_bound_download(kg_engine *eng, int32_t node, kg_pod_row *rows, int32_t *priority, int64_t *start_ns,
+                            int32_t cap, int32_t *n);   /* in the caller's order; for tests and debugging */
+
+/* The dry run of one (preemptor, node) pair: preempt.go:111-215 restated, without PodDisruptionBudgets.
+ *   1. a row that is not KG_NODE_VALID: KG_PRE_ABSENT.
+ *   2. potential victims (canPreempt, preempt.go:283-294): not KG_POD_NON_PREEMPTIBLE, priority below the preemptor's,
+ *      the same quota index (-1 equals -1).  None: KG_PRE_NO_VICTIMS ("No victims found", UnschedulableAndUnresolvable).
+ *   3. all of them are removed from a copy of the row (requested -= request, nonzero_requested -= nonzero_request,
+ *      pod_count - 1; LoadAware's la_used* stay: RemovePod does not reach the pod-assign cache; only Score reads
+ *      NonZeroRequested, so the verdicts do not depend on it) and, when the quota
+ *      check is active (ElasticQuota enabled and the preemptor's quota >= 0), from the group's `used`
+ *      (quotav1.SubtractWithNonNegativeResult: max(0, used - numa_request) per resource, keys united; the ancestors
+ *      and non_preemptible_used are neither read nor changed).
+ *   4. Filter on the reduced row - exactly the verdict kg_row_why == 0 gives for it (kg_preempt adds the pod's
+ *      eligibility class) - fails: KG_PRE_UNFIT.
+ *   5. reprieve in importance order: the pod is added back to the row and to `used`; if the preemptor no longer fits
+ *      it is removed again and becomes a victim; then, with the quota check active, used + numa_request must stay
+ *      within used_limit on the resources both name (kg_quota_set's PreFilter compare on the evolving `used`): if not,
+ *      a pod that still fits is removed and becomes a victim, and for a pod removed just above the reference removes
+ *      it a second time, NodeInfo.RemovePod errors and the node is dropped: KG_PRE_ERROR (pinned, not repaired).
+ *   6. KG_PRE_CANDIDATE with the victim mask (caller positions), n_victims, hi_prio (the highest victim priority),
+ *      prio_sum (sum of priority + 2^31) and earliest_ns (the earliest start among the victims of priority hi_prio).  A
+ *      candidate may have no victim: the pod fitted all along.
+ * Every status but KG_PRE_CANDIDATE leaves the mask and the stats zero.
+ * kg_row_preempt is the host entry (no engine; it ignores kg_pod_row.elig_class, as kg_row_why): bound[n_bound] in the
+ * caller's order, quotas NULL <=> none.  KG_ERR_INVALID_ARG for null pointers, KG_ERR_RANGE for n_bound outside
+ * 0..KG_BOUND_MAX_PER_NODE or an active quota index at or past n_quotas, KG_ERR_UNSUPPORTED with KG_PLUGIN_NUMA.
+ * Out of scope (a caller that needs one of these keeps the host path): PodDisruptionBudgets (a PDB that matches a
+ * potential victim), nominated pods (RunFilterPluginsWithNominatedPods' add-back), PodEligibleToPreemptOthers (a host
+ * check on one node), extenders, the eviction itself (the feeders deliver its pod deletes), NodeNUMAResource
+ * (filterAmplifiedCPUs reads NodeInfo.Requested, so its verdict moves with every removal) and Reservation with slots
+ * loaded (AddPod / RemovePod of its own, reservation/plugin.go:254-300). */
+#define KG_PRE_CANDIDATE 0
+#define KG_PRE_ABSENT 1
+#define KG_PRE_NO_VICTIMS 2
+#define KG_PRE_UNFIT 3
+#define KG_PRE_ERROR 4
+kg_status kg_row_preempt(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *bound, const int32_t *bound_priority,
+                         const int64_t *bound_start_ns, int32_t n_bound, const kg_pod_row *pod, int32_t pod_priority,
+                         const kg_quota *quotas /* NULL <=> none */, int32_t n_quotas, int64_t now_ns,
+                         int32_t *status, uint64_t victims[2], int64_t stats[4] /* n_victims, hi_prio, prio_sum, earliest_ns */);
+
+/* The dry run of up to KG_PREEMPT_MAX_PODS preemptors against every node of the shard (kg_set_shard; node indices are
+ * global) in one call, and the node to preempt on.  The pod rows travel with the call (as kg_diagnose); the batch
+ * uploaded with kg_pods_set is neither read nor replaced.  Nothing is mutated: rows, table, quota state, generation and
+ * kg_counters.placed / resolved stay.  The quota check reads group `used` / `used_limit` as the device holds them
+ * (kg_quota_set and the commits since).
+ *   pick  [n][KG_PREEMPT_PICK_WORDS] int64 (required): node (-1: no candidate), n_victims, hi_prio, prio_sum,
+ *         earliest_ns, victim mask word 0, word 1, n_candidates (the KG_PRE_CANDIDATE nodes of the shard).  With node
+ *         -1 every other word is 0.  The pick among the candidates restates upstream pickOneNodeForPreemption: a node
+ *         with no victim wins outright, then the lowest hi_prio, the lowest prio_sum, the fewest victims, the latest
+ *         earliest_ns, and last the lowest node index (upstream: map order; the project's tie rule).
+ *   plane [n][64 * W] uint32 (may be NULL): status | n_victims << 8 | n_potential << 16 per node, kg_diagnose's plane
+ *         contract - W = ceil((E - B) / 64), column c <=> node B + c, pad columns unspecified, nothing outside
+ *         [n][64 * W] written, a device pointer 16-byte aligned, no pre-zeroing needed.
+ * out_on_device != 0: both are device pointers on the engine's device (pick 8-byte aligned).  The call returns after
+ * the launches completed either way.  Exact integers, identical from run to run: per-(pod, tile) best records, then a
+ * reduction over the tiles; no atomics.  An empty shard writes node = -1 picks and launches nothing; n = 0 is a no-op.
+ * kg_preempt_merge applies the same order on the host to the picks of several shards or ranks for the same pods
+ * (picks [n_lists][n][8]); n_candidates is summed.  KG_ERR_INVALID_ARG for n_lists < 1, n < 0 or null pointers.
+ * Counters: eval_calls + 1, evals + n * (E - B), out_bytes by the bytes of pick and plane, h2d_bytes by the upload.
+ * Errors (nothing launched, counters untouched): KG_ERR_INVALID_ARG for flags != 0, n < 0 or a null pods / priority /
+ * pick with n > 0; KG_ERR_RANGE for n > KG_PREEMPT_MAX_PODS, a row outside the engine bounds or an elig_class outside
+ * the loaded classes; KG_ERR_STATE without a snapshot, without a bound table, on a stale engine, or for a quota index
+ * without a kg_quota_set group; KG_ERR_UNSUPPORTED with KG_PLUGIN_NUMA enabled, or Reservation enabled with slots
+ * loaded. */
+#define KG_PREEMPT_MAX_PODS 64
+#define KG_PREEMPT_PICK_WORDS 8
+kg_status kg_preempt(kg_engine *eng, const kg_pod_row *pods, const int32_t *priority, int32_t n, int64_t now_ns, uint32_t flags /* 0 */,
+                     int64_t *pick   /* [n][8], required */,
+                     uint32_t *plane /* [n][64 * W], may be NULL */, int32_t out_on_device);
+kg_status kg_preempt_merge(const int64_t *picks /* [n_lists][n][8] */, int32_t n_lists, int32_t n, int64_t *out /* [n][8] */);
 
 /* Measurement: when on, every k_eval launch (kg_eval, kg_place_chunk_eval) is bracketed by a
  * pair of HIP events on the engine stream (ring of 256).  kg_eval_kernel_times writes the

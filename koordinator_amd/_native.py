@@ -69,6 +69,12 @@ DIAG_MAX_PODS = 256
 UNRESERVE_MAX = 4096   # KG_UNRESERVE_MAX: entries of one kg_unreserve call
 CAND_MAX_K = 64          # KG_CAND_MAX_K: longest kg_candidates list
 CAND_MAX_PODS = 256      # KG_CAND_MAX_PODS: pods of one kg_candidates call
+# preemption dry run (kg_row_preempt / kg_preempt): the per-pair status, the table and call limits, the pick layout
+PRE_CANDIDATE, PRE_ABSENT, PRE_NO_VICTIMS, PRE_UNFIT, PRE_ERROR = range(5)
+BOUND_MAX_PER_NODE = 128     # KG_BOUND_MAX_PER_NODE: bound pods of one node (bits of a victim mask)
+PREEMPT_MAX_PODS = 64        # KG_PREEMPT_MAX_PODS: preemptors of one kg_preempt call
+PREEMPT_PICK_WORDS = 8       # KG_PREEMPT_PICK_WORDS: node, n_victims, hi_prio, prio_sum, earliest_ns, mask 0, mask 1, n_candidates
+START_NS_NONE = (1 << 63) - 1   # a bound pod without Status.StartTime (upstream: Now(), later than every real start)
 NODE_VALID, NODE_HAS_METRIC, NODE_HAS_UPDATE_TIME, NODE_LA_PASS_NONPROD, NODE_LA_PASS_PROD = 0x1, 0x2, 0x4, 0x8, 0x10
 NODE_NUMA_OPTIONS, NODE_NUMA_TOPO_VALID, NODE_NUMA_TOPO_INVALID = 0x40, 0x80, 0x100
 
@@ -254,7 +260,8 @@ EXPORTED = [
     "kg_place_sharded", "kg_counters_get", "kg_counters_reset", "kg_comm_init_loopback", "kg_comm_kind",
     "kg_cycle_one", "kg_batch_slot_map", "kg_pods_spill_count", "kg_elig_set", "kg_elig_update",
     "kg_pods_restricted_count", "kg_row_why", "kg_diagnose", "kg_row_unreserve", "kg_row_numa_alloc", "kg_unreserve",
-    "kg_candidates", "kg_candidates_merge",
+    "kg_candidates", "kg_candidates_merge", "kg_bound_set", "kg_bound_update", "kg_bound_download", "kg_row_preempt",
+    "kg_preempt", "kg_preempt_merge",
 ]
 
 _lib = None
@@ -315,6 +322,11 @@ def lib() -> ctypes.CDLL:
         "kg_unreserve": (i32, [vp, vp, vp, i32, ctypes.c_uint32, vp, vp, vp]),
         "kg_candidates": (i32, [vp, vp, i32, i64, i32, ctypes.c_uint32, vp, vp, vp, i32]),
         "kg_candidates_merge": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        "kg_bound_set": (i32, [vp, vp, vp, vp, vp, i32]), "kg_bound_update": (i32, [vp, i32, vp, vp, vp, i32]),
+        "kg_bound_download": (i32, [vp, i32, vp, vp, vp, i32, vp]),
+        "kg_row_preempt": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i64, vp, vp, vp]),
+        "kg_preempt": (i32, [vp, vp, vp, i32, i64, ctypes.c_uint32, vp, vp, i32]),
+        "kg_preempt_merge": (i32, [vp, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         if host_only and not hasattr(L, name):

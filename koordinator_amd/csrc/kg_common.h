@@ -1837,3 +1837,181 @@ KG_HD uint32_t kg_pod_why(const kg_consts &c, const kg_quota *qs, int32_t n_quot
     if ((p.flags & KGP_RSV_REQUIRED) && !rsv_slots) w |= KG_WHY_POD_RSV_REQUIRED;
     return w;
 }
+
+// ---- preemption dry run (kg_row_preempt, kg_preempt) ------------------------------------------
+// ElasticQuota's SelectVictimsOnNode (elasticquota/preempt.go:111-215) for one (preemptor, node) pair, without
+// PodDisruptionBudgets: the potential victims (canPreempt, :283-294) are removed, Filter runs on what is left, and the
+// victims are added back one by one in util.MoreImportantPod order, each kept when the preemptor still fits and the
+// group's evolving `used` still admits it.  Only NodeResourcesFit reads what RemovePod / AddPodInfo change (Requested
+// and len(Pods)), so the rest of the Filter verdict (the row's validity, the eligibility class, LoadAware) is computed
+// once by the caller (`rest_ok`).  NonZeroRequested moves with the pods too, but only Score reads it.
+// The node's list is read through `Src` in importance order (position s < n): the host entry reads kg_pod_row arrays
+// through a sorted index, k_preempt the slot-major table.  Every loop over KG_NUM_RES is unrolled over constant
+// indices, so on the device the running values stay in registers.
+// a value every lane of the wave holds alike (it derives from the staged pod row): read into a scalar register on the
+// device, so the branches on it are scalar branches and the loads they guard are skipped, not masked
+#if defined(__HIP_DEVICE_COMPILE__)
+#define KG_WAVE_UNIFORM(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
+#else
+#define KG_WAVE_UNIFORM(x) ((uint32_t)(x))
+#endif
+struct kg_pre_state {
+    int64_t free_[KG_NUM_RES];   // Allocatable - Requested of the evolving NodeInfo
+    int64_t used[KG_NUM_RES];    // postFilterState.used of the preemptor's group (absent keys read 0)
+    int32_t pod_count;           // len(NodeInfo.Pods)
+};
+struct kg_pre_out {
+    int32_t status;              // KG_PRE_*
+    int32_t n_potential;
+    int32_t n_victims;
+    int32_t hi_prio;
+    int64_t prio_sum;
+    int64_t earliest_ns;
+    uint64_t victims[2];         // caller positions
+};
+// what the quota re-check reads of the preemptor's group: absent when ElasticQuota is off or the pod has no group
+struct kg_pre_quota {
+    int64_t limit[KG_NUM_RES];   // used_limit
+    uint32_t mask;               // resources both the limit and the preemptor's request name (kg_quota_leq)
+    uint32_t active;
+};
+
+// the resources whose free amount a Fit compare of this preemptor reads: the others are neither loaded nor tracked
+KG_HD uint32_t kg_pre_fit_res(const kg_consts &c, const kg_pod_dev &p) {
+    if (!(c.plugins & KG_PLUGIN_FIT) || !(p.flags & KG_POD_HAS_REQUEST)) return 0u;
+    return 0x7u | (p.request_present & ((1u << KG_NUM_RES) - 1u));
+}
+// NodeResourcesFit on the evolving state: kg_pair_why's Fit bits, as one verdict
+KG_HD bool kg_pre_fits(const kg_consts &c, const kg_pod_dev &p, const kg_pre_state &s, int32_t allowed) {
+    if (!(c.plugins & KG_PLUGIN_FIT)) return true;
+    bool ok = (int64_t)s.pod_count + 1 <= (int64_t)allowed;
+    if (p.flags & KG_POD_HAS_REQUEST) {
+#pragma unroll
+        for (int r = 0; r < KG_NUM_RES; r++)
+            if (r < 3 || ((p.request_present >> r) & 1u)) ok = ok && p.req[r] <= s.free_[r];
+    }
+    return ok;
+}
+// Mask(used + podReq, names(podReq)) <= usedLimit on the evolving `used`
+KG_HD bool kg_pre_quota_ok(const kg_pod_dev &p, const kg_pre_state &s, const kg_pre_quota &q) {
+    bool ok = true;
+#pragma unroll
+    for (int r = 0; r < KG_NUM_RES; r++)
+        if ((q.mask >> r) & 1u) ok = ok && p.numa_req[r] + s.used[r] <= q.limit[r];
+    return ok;
+}
+// NodeInfo.RemovePod + quotav1.SubtractWithNonNegativeResult / NodeInfo.AddPodInfo + quotav1.Add of list entry `s`.
+// `res`: the resources some later check reads (the Fit compares and the quota mask): the others are not loaded.
+template <class Src>
+KG_HD void kg_pre_remove(kg_pre_state &st, const Src &src, int s, uint32_t res, uint32_t qres, uint32_t present) {
+#pragma unroll
+    for (int r = 0; r < KG_NUM_RES; r++) {
+        if ((res >> r) & 1u) st.free_[r] += src.req(s, r);
+        if (((qres & present) >> r) & 1u) st.used[r] = kg_sub_nonneg(st.used[r], src.numa_req(s, r));
+    }
+    st.pod_count -= 1;
+}
+template <class Src>
+KG_HD void kg_pre_add(kg_pre_state &st, const Src &src, int s, uint32_t res, uint32_t qres, uint32_t present) {
+#pragma unroll
+    for (int r = 0; r < KG_NUM_RES; r++) {
+        if ((res >> r) & 1u) st.free_[r] -= src.req(s, r);
+        if (((qres & present) >> r) & 1u) st.used[r] += src.numa_req(s, r);
+    }
+    st.pod_count += 1;
+}
+
+// Pick order of the candidates (upstream pickOneNodeForPreemption without PDBs): a node with no victim first, then the
+// lowest highest-victim priority, the lowest priority sum, the fewest victims, the latest earliest start among the
+// highest-priority victims, the lowest node index.  node < 0: no candidate (never better).
+KG_HD bool kg_pre_better(int64_t a_node, int64_t a_nv, int64_t a_hi, int64_t a_sum, int64_t a_early, int64_t b_node,
+                         int64_t b_nv, int64_t b_hi, int64_t b_sum, int64_t b_early) {
+    if (a_node < 0) return false;
+    if (b_node < 0) return true;
+    if ((a_nv == 0) != (b_nv == 0)) return a_nv == 0;
+    if (a_hi != b_hi) return a_hi < b_hi;
+    if (a_sum != b_sum) return a_sum < b_sum;
+    if (a_nv != b_nv) return a_nv < b_nv;
+    if (a_early != b_early) return a_early > b_early;
+    return a_node < b_node;
+}
+
+// The dry run of one pair.  `pp` / `g`: the preemptor's priority and quota group as its row names it (the canPreempt
+// compare holds with ElasticQuota off too; -1 equals -1).  `valid`: the row is KG_NODE_VALID; `rest_ok`: every part of
+// the Filter but NodeResourcesFit passes.  `st` holds the node's free amounts (of the resources kg_pre_fit_res names),
+// pod count and the group's used (of the resources of q.mask) on entry.
+template <class Src>
+KG_HD void kg_preempt_pair(const kg_consts &c, const kg_pod_dev &p, int32_t pp, int32_t g, bool valid, bool rest_ok,
+                           int32_t allowed, kg_pre_state &st, const kg_pre_quota &q, const Src &src, int32_t n,
+                           kg_pre_out &o) {
+    o.status = KG_PRE_ABSENT;
+    o.n_potential = o.n_victims = o.hi_prio = 0;
+    o.prio_sum = o.earliest_ns = 0;
+    o.victims[0] = o.victims[1] = 0;
+    if (!valid) return;
+    const uint32_t res = KG_WAVE_UNIFORM(kg_pre_fit_res(c, p));
+    const uint32_t qres = KG_WAVE_UNIFORM(q.active ? q.mask : 0u);
+    const bool q_on = KG_WAVE_UNIFORM(q.active) != 0u;
+    // the potential victims, by position in importance order, all removed
+    uint64_t pot0 = 0, pot1 = 0;
+    int32_t np = 0;
+    for (int s = 0; s < n; s++) {
+        if (src.non_preemptible(s) || src.priority(s) >= pp || src.quota(s) != g) continue;
+        if (s < 64) pot0 |= 1ull << s;
+        else pot1 |= 1ull << (s - 64);
+        np++;
+        kg_pre_remove(st, src, s, res, qres, src.numa_present(s));
+    }
+    o.n_potential = np;
+    if (np == 0) {
+        o.status = KG_PRE_NO_VICTIMS;
+        return;
+    }
+    if (!rest_ok || !kg_pre_fits(c, p, st, allowed)) {
+        o.status = KG_PRE_UNFIT;
+        return;
+    }
+    // reprieve in importance order
+    int32_t nv = 0, hi = 0;
+    int64_t sum = 0, early = 0;
+    uint64_t v0 = 0, v1 = 0;
+    for (int s = 0; s < n; s++) {
+        if (!(((s < 64 ? pot0 >> s : pot1 >> (s - 64))) & 1ull)) continue;
+        const uint32_t present = src.numa_present(s);
+        kg_pre_add(st, src, s, res, qres, present);
+        bool victim = false;
+        if (!kg_pre_fits(c, p, st, allowed)) {
+            kg_pre_remove(st, src, s, res, qres, present);
+            victim = true;
+        }
+        if (q_on && !kg_pre_quota_ok(p, st, q)) {
+            if (victim) {   // the reference removes the pod a second time: NodeInfo.RemovePod errors, the node is dropped
+                o.status = KG_PRE_ERROR;
+                return;
+            }
+            kg_pre_remove(st, src, s, res, qres, present);
+            victim = true;
+        }
+        if (!victim) continue;
+        const int32_t pr = src.priority(s);
+        const int64_t t = src.start_ns(s);
+        const int pos = src.position(s);
+        if (pos < 64) v0 |= 1ull << pos;
+        else v1 |= 1ull << (pos - 64);
+        if (nv == 0 || pr > hi) {
+            hi = pr;
+            early = t;
+        } else if (pr == hi && t < early) {
+            early = t;
+        }
+        sum += (int64_t)pr + 2147483648LL;
+        nv++;
+    }
+    o.status = KG_PRE_CANDIDATE;
+    o.n_victims = nv;
+    o.hi_prio = hi;
+    o.prio_sum = sum;
+    o.earliest_ns = early;
+    o.victims[0] = v0;
+    o.victims[1] = v1;
+}

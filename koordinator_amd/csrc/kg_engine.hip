@@ -88,6 +88,10 @@
 //   125-126 k_unreserve_quota         released (call index, read), quota group of a chain
 //   127-128 k_cand                    pod row (read; k_cand_merge too), per-(pod, tile) lists and counts
 //   129-132 k_cand_merge              per-(pod, tile) lists and counts (read), keys, scores, n_feasible
+//   133-137 k_preempt                 pod row (read), bound table slot and node (read), status plane, per-(pod, tile)
+//                                     records, quota group (read)
+//   138-139 k_preempt_pick            per-(pod, tile) records (read), pick
+//   140-141 k_bound_update            staged record (read), bound table slot and node
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -3731,6 +3735,284 @@ __global__ __launch_bounds__(64) void k_why_reduce(kg_consts c, const uint32_t *
 }
 
 // ---------------------------------------------------------------------------------------
+// kg_preempt: the preemption dry run of listed pods over the shard (k_preempt) and the node to preempt on
+// ---------------------------------------------------------------------------------------
+// The bound-pod table (kg_bound_set): slot-major struct-of-arrays over the nodes, tab[(s * KG_BOUND_FIELDS + f) * cap +
+// node] with s the pod's place in its node's list in importance order, so the lanes of a wave (consecutive nodes) read
+// "field f of slot s of my node" as one coalesced access.  Fields: 0-11 request, 12-23 numa_request, 24-25
+// nonzero_request, 26 start_ns, 27 priority | (caller position | non-preemptible << 8) << 32, 28 quota |
+// (request_present | numa_request_present << 12) << 32.  Per node the summary planes: its list length, and the count and
+// the lowest priority of its preemptible pods, which let a lane answer NO_VICTIMS without reading a record.
+#define KG_BOUND_FIELDS 29
+#define KG_BF_NUMA 12
+#define KG_BF_NONZERO 24
+#define KG_BF_START 26
+#define KG_BF_META 27
+#define KG_BF_KEYS 28
+struct BoundTab {
+    const int64_t *tab;       // [max_per_node][KG_BOUND_FIELDS][cap]
+    const int32_t *count;     // [cap] pods of the node's list
+    const int32_t *n_pre;     // [cap] those without KG_POD_NON_PREEMPTIBLE
+    const int32_t *min_prio;  // [cap] their lowest priority (INT32_MAX: none)
+    int64_t cap;
+    int32_t max_per_node;
+};
+// one node's list as kg_preempt_pair reads it
+struct BoundSrc {
+    const int64_t *__restrict__ tab;
+    int64_t cap, node;
+    int32_t max_per_node;
+    __device__ __forceinline__ int64_t f(int s, int fld) const {
+        return KG_IN2(134, s, max_per_node, node, cap) ? tab[((int64_t)s * KG_BOUND_FIELDS + fld) * cap + node] : 0;
+    }
+    __device__ __forceinline__ int64_t req(int s, int r) const { return f(s, r); }
+    __device__ __forceinline__ int64_t numa_req(int s, int r) const { return f(s, KG_BF_NUMA + r); }
+    __device__ __forceinline__ uint32_t numa_present(int s) const { return (uint32_t)((uint64_t)f(s, KG_BF_KEYS) >> 44) & 0xFFFu; }
+    __device__ __forceinline__ bool non_preemptible(int s) const { return (((uint64_t)f(s, KG_BF_META) >> 40) & 1ull) != 0; }
+    __device__ __forceinline__ int32_t quota(int s) const { return (int32_t)(uint32_t)(uint64_t)f(s, KG_BF_KEYS); }
+    __device__ __forceinline__ int32_t priority(int s) const { return (int32_t)(uint32_t)(uint64_t)f(s, KG_BF_META); }
+    __device__ __forceinline__ int64_t start_ns(int s) const { return f(s, KG_BF_START); }
+    __device__ __forceinline__ int position(int s) const { return (int)(((uint64_t)f(s, KG_BF_META) >> 32) & 0xFFull); }
+};
+
+struct PreArgs {
+    int64_t node_end;            // the shard's end
+    int64_t col_begin;           // its begin: column c of a plane row <=> node col_begin + c
+    int64_t stride;              // words per plane row: 64 * W
+    int64_t now_ns;
+    int32_t tile_begin, shard_tiles;
+    int32_t n_groups, pods_per_group;
+    int32_t n_pods;
+    int32_t n_quota;
+    const kg_quota *quota;       // device quota state (nullptr: ElasticQuota off or no groups)
+    BoundTab bt;
+};
+// per staged preemptor: its priority and group as the row names them, and what the quota re-check reads
+struct PrePod {
+    int64_t used[KG_NUM_RES];
+    kg_pre_quota q;
+    int32_t prio, group;
+};
+// a pick record in flight: the order of kg_pre_better
+struct PreRec {
+    int64_t node, nv, hi, sum, early;
+};
+__device__ __forceinline__ void pre_wave_best(PreRec &r) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        PreRec o;
+        o.node = __shfl_xor(r.node, off, 64);
+        o.nv = __shfl_xor(r.nv, off, 64);
+        o.hi = __shfl_xor(r.hi, off, 64);
+        o.sum = __shfl_xor(r.sum, off, 64);
+        o.early = __shfl_xor(r.early, off, 64);
+        if (kg_pre_better(o.node, o.nv, o.hi, o.sum, o.early, r.node, r.nv, r.hi, r.sum, r.early)) r = o;
+    }
+}
+#define KG_PRE_WAVES (KG_BLOCK / 64)
+#define KG_PRE_SLOTS (2 * KG_PRE_WAVES)   // wave-best records of one (pod, tile): a wave x its two 64-node halves
+
+// k_why's geometry: one workgroup = one 1024-node tile x a group of the pods (XCD-aware order), pod rows staged
+// KG_SPILL_CHUNK at a time in LDS with their quota group's used / used_limit.  One lane per (preemptor, node): a wave
+// takes its 128 nodes in two halves, loads a node's pod counts, derived flags and list summary once, and runs
+// kg_preempt_pair for every staged pod with the running values in registers: the free amounts of the resources the
+// pod's Fit compares read (the free_ planes: Allocatable - Requested, exact int64) and the group's `used`.  A lane whose node has no preemptible pod below the preemptor's priority
+// is done without reading a record; otherwise the lanes of a wave run as long as the longest list among them.
+// PLANE: status | n_victims << 8 | n_potential << 16 as coalesced 32-bit stores, a 64-node segment only inside the
+// padded row.  Pick: the wave's best candidate by shuffles, the winning lane writes its record and mask to LDS; a wave
+// per pod then reduces the workgroup's 16 records and stores the (pod, tile) record and candidate count into `slab`
+// [n][shard_tiles][8] with plain stores, every word of it: no atomics.
+template <bool PLANE>
+__global__ __launch_bounds__(KG_BLOCK) void k_preempt(kg_consts c, kg_planes pl, PreArgs a,
+                                                      const kg_pod_dev *__restrict__ pods,
+                                                      const int32_t *__restrict__ prio, const int32_t *__restrict__ group,
+                                                      uint32_t *__restrict__ plane, int64_t *__restrict__ slab) {
+    __shared__ __attribute__((aligned(16))) kg_pod_dev lp[KG_SPILL_CHUNK];
+    __shared__ PrePod lq[KG_SPILL_CHUNK];
+    __shared__ int64_t lrec[KG_SPILL_CHUNK][KG_PRE_SLOTS][8];
+    __shared__ uint32_t lcand[KG_SPILL_CHUNK][KG_PRE_SLOTS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x, xcd = b % KG_XCDS, rr = b / KG_XCDS;
+    const int tile_rel = (rr / a.n_groups) * KG_XCDS + xcd, grp = rr % a.n_groups;
+    if (tile_rel >= a.shard_tiles) return;   // grid padded to a multiple of 8 tiles; block-uniform
+    const int tile = a.tile_begin + tile_rel;
+    const int64_t wave_base = (int64_t)tile * KG_TILE + wave * 128;
+    const bool la_on = (c.plugins & KG_PLUGIN_LOADAWARE) != 0;
+    constexpr int POD_DW = (int)(sizeof(kg_pod_dev) / 4);
+    const int gb = grp * a.pods_per_group;
+    const int ge = min(gb + a.pods_per_group, a.n_pods);
+    for (int q0 = gb; q0 < ge; q0 += KG_SPILL_CHUNK) {
+        const int nq = min(KG_SPILL_CHUNK, ge - q0);
+        for (int k = tid; k < nq * POD_DW; k += KG_BLOCK) {
+            const int j = k / POD_DW, w = k - j * POD_DW;
+            reinterpret_cast<uint32_t *>(&lp[j])[w] =
+                KG_IN(133, q0 + j, a.n_pods) ? reinterpret_cast<const uint32_t *>(pods + q0 + j)[w] : 0u;
+        }
+        if (tid < nq && KG_IN(133, q0 + tid, a.n_pods)) {   // (reads the global row: lp is still being staged)
+            PrePod &d = lq[tid];
+            const int32_t g = group[q0 + tid];
+            d.prio = prio[q0 + tid];
+            d.group = g;
+            const bool on = (c.plugins & KG_PLUGIN_ELASTICQUOTA) && a.quota && g >= 0 && KG_IN(137, g, a.n_quota);
+            d.q.active = on ? 1u : 0u;
+            d.q.mask = on ? (a.quota[g].used_limit.present & pods[q0 + tid].numa_present & ((1u << KG_NUM_RES) - 1u)) : 0u;
+            for (int r = 0; r < KG_NUM_RES; r++) {
+                d.used[r] = on ? kg_rl_get(a.quota[g].used, r) : 0;
+                d.q.limit[r] = on ? a.quota[g].used_limit.v[r] : 0;
+            }
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int h = 0; h < 2; h++) {
+            const int64_t node = wave_base + 64 * h + lane;
+            const bool in = node < a.node_end;
+            const uint32_t df = in ? pl.dflags[node] : 0u;
+            const bool expired = la_on && kg_metric_expired(c, df, in ? pl.metric_ns[node] : 0, a.now_ns);
+            const int32_t cnt0 = in ? pl.rows[node].pod_count : 0, allowed = in ? pl.rows[node].allowed_pods : 0;
+            const int32_t nb = in ? a.bt.count[node] : 0, npre = in ? a.bt.n_pre[node] : 0;
+            const int32_t minp = in ? a.bt.min_prio[node] : INT32_MAX;
+            const BoundSrc src{a.bt.tab, a.bt.cap, node, a.bt.max_per_node};
+            const int64_t col = wave_base + 64 * h - a.col_begin;   // wave-uniform
+            [[maybe_unused]] const bool seg = col < a.stride;
+            for (int j = 0; j < nq; j++) {
+                const kg_pod_dev &p = lp[j];
+                const PrePod &pq = lq[j];
+                kg_pre_out o;
+                const bool valid = (df & KGD_VALID) != 0;
+                if (valid && (npre == 0 || minp >= pq.prio)) {   // no preemptible pod below the preemptor: no record read
+                    o.status = KG_PRE_NO_VICTIMS;
+                    o.n_potential = o.n_victims = o.hi_prio = 0;
+                    o.prio_sum = o.earliest_ns = 0;
+                    o.victims[0] = o.victims[1] = 0;
+                } else {
+                    // the free amounts the pod's Fit compares read (a coalesced load per resource, wave-uniform choice)
+                    // and the group's used of the resources the re-check reads
+                    const uint32_t fres = kg_pre_fit_res(c, p);
+                    kg_pre_state st;
+#pragma unroll
+                    for (int r = 0; r < KG_NUM_RES; r++) {
+                        st.free_[r] = (in && ((fres >> r) & 1u)) ? pl.free_[r * pl.cap + node] : 0;
+                        st.used[r] = ((pq.q.mask >> r) & 1u) ? pq.used[r] : 0;
+                    }
+                    st.pod_count = cnt0;
+                    const bool rest_ok = kg_elig_ok(pl, p, node) && kg_why_la(c, df, expired, p) == 0u;
+                    kg_preempt_pair(c, p, pq.prio, pq.group, valid, rest_ok, allowed, st, pq.q, src, valid ? nb : 0, o);
+                }
+                const bool cand = in && o.status == KG_PRE_CANDIDATE;
+                if constexpr (PLANE) {
+                    const int pi = q0 + j;
+                    if (seg && KG_IN2(135, pi, a.n_pods, col + lane, a.stride))
+                        plane[(int64_t)pi * a.stride + col + lane] =
+                            (uint32_t)o.status | ((uint32_t)(cand ? o.n_victims : 0) << 8) | ((uint32_t)o.n_potential << 16);
+                }
+                PreRec best{cand ? node : -1, o.n_victims, o.hi_prio, o.prio_sum, o.earliest_ns};
+                pre_wave_best(best);
+                const int slot = wave * 2 + h;
+                if (best.node < 0 ? lane == 0 : (cand && node == best.node)) {
+                    int64_t *d = lrec[j][slot];
+                    d[0] = best.node;
+                    d[1] = best.node < 0 ? 0 : best.nv;
+                    d[2] = best.node < 0 ? 0 : best.hi;
+                    d[3] = best.node < 0 ? 0 : best.sum;
+                    d[4] = best.node < 0 ? 0 : best.early;
+                    d[5] = best.node < 0 ? 0 : (int64_t)o.victims[0];
+                    d[6] = best.node < 0 ? 0 : (int64_t)o.victims[1];
+                    d[7] = 0;
+                }
+                const uint32_t nc = (uint32_t)__popcll(__ballot(cand));
+                if (lane == 0) lcand[j][slot] = nc;
+            }
+        }
+        __syncthreads();
+        for (int j = wave; j < nq; j += KG_PRE_WAVES) {   // a wave per pod
+            const int pi = q0 + j;
+            const bool has = lane < KG_PRE_SLOTS;
+            PreRec best{has ? lrec[j][has ? lane : 0][0] : -1, 0, 0, 0, 0};
+            if (has) {
+                best.nv = lrec[j][lane][1];
+                best.hi = lrec[j][lane][2];
+                best.sum = lrec[j][lane][3];
+                best.early = lrec[j][lane][4];
+            }
+            const int64_t mine = best.node;
+            uint32_t nc = has ? lcand[j][lane] : 0u;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) nc += __shfl_xor(nc, off, 64);
+            pre_wave_best(best);
+            if (best.node < 0 ? lane == 0 : (has && mine == best.node)) {
+                if (KG_IN2(136, pi, a.n_pods, tile_rel, a.shard_tiles)) {
+                    int64_t *d = slab + ((int64_t)pi * a.shard_tiles + tile_rel) * 8;
+                    d[0] = best.node;
+                    d[1] = best.node < 0 ? 0 : best.nv;
+                    d[2] = best.node < 0 ? 0 : best.hi;
+                    d[3] = best.node < 0 ? 0 : best.sum;
+                    d[4] = best.node < 0 ? 0 : best.early;
+                    d[5] = best.node < 0 ? 0 : lrec[j][has ? lane : 0][5];
+                    d[6] = best.node < 0 ? 0 : lrec[j][has ? lane : 0][6];
+                    d[7] = (int64_t)nc;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// The pick of each pod over the tiles' records: a wave per pod, lane t takes tiles t, t + 64, ..., the wave's best by
+// the same shuffles, the candidate counts summed; every word of pick[p] is written (node -1: the others 0).
+__global__ __launch_bounds__(64) void k_preempt_pick(const int64_t *__restrict__ slab, int32_t n_pods, int32_t tiles,
+                                                     int64_t *__restrict__ pick) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    if (p >= n_pods) return;   // block-uniform
+    PreRec best{-1, 0, 0, 0, 0};
+    int64_t m0 = 0, m1 = 0, nc = 0;
+    for (int t = lane; t < tiles; t += 64) {
+        if (!KG_IN2(138, p, n_pods, t, tiles)) continue;
+        const int64_t *d = slab + ((int64_t)p * tiles + t) * 8;
+        nc += d[7];
+        if (kg_pre_better(d[0], d[1], d[2], d[3], d[4], best.node, best.nv, best.hi, best.sum, best.early)) {
+            best = PreRec{d[0], d[1], d[2], d[3], d[4]};
+            m0 = d[5];
+            m1 = d[6];
+        }
+    }
+    const int64_t mine = best.node;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) nc += __shfl_xor(nc, off, 64);
+    pre_wave_best(best);
+    if ((best.node < 0 ? lane == 0 : mine == best.node) && KG_IN(139, p, n_pods)) {
+        int64_t *d = pick + (int64_t)p * KG_PREEMPT_PICK_WORDS;
+        const bool none = best.node < 0;
+        d[0] = best.node;
+        d[1] = none ? 0 : best.nv;
+        d[2] = none ? 0 : best.hi;
+        d[3] = none ? 0 : best.sum;
+        d[4] = none ? 0 : best.early;
+        d[5] = none ? 0 : m0;
+        d[6] = none ? 0 : m1;
+        d[7] = none ? 0 : nc;
+    }
+}
+
+// kg_bound_update: one node's staged list ([n][KG_BOUND_FIELDS], importance order) scattered into its column of the
+// table, and its summary
+__global__ void k_bound_update(int64_t *__restrict__ tab, int32_t *__restrict__ count, int32_t *__restrict__ n_pre,
+                               int32_t *__restrict__ min_prio, int64_t cap, int32_t max_per_node, int64_t node,
+                               const int64_t *__restrict__ staged, int32_t n, int32_t pre, int32_t minp) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k == 0 && KG_IN(141, node, cap)) {
+        count[node] = n;
+        n_pre[node] = pre;
+        min_prio[node] = minp;
+    }
+    if (k >= n * KG_BOUND_FIELDS) return;
+    const int s = k / KG_BOUND_FIELDS, f = k - s * KG_BOUND_FIELDS;
+    if (KG_IN(140, k, (int64_t)n * KG_BOUND_FIELDS) && KG_IN2(141, s, max_per_node, node, cap))
+        tab[((int64_t)s * KG_BOUND_FIELDS + f) * cap + node] = staged[k];
+}
+
+// ---------------------------------------------------------------------------------------
 // kg_candidates: the k best feasible nodes of listed pods over the shard, with the engine plugins' scores
 // ---------------------------------------------------------------------------------------
 struct CandArgs {
@@ -4095,6 +4377,16 @@ struct kg_engine {
     void *cand_mem = nullptr;
     size_t cand_bytes = 0;
     void *cand_host = nullptr;
+    // the bound-pod table (kg_bound_set): table and summary planes in one allocation, sized for the snapshot's cap
+    void *bound_mem = nullptr;
+    int64_t *bound_tab = nullptr;
+    int32_t *bound_count = nullptr, *bound_npre = nullptr, *bound_minprio = nullptr;
+    int32_t bound_max = 0;
+    // kg_preempt: the call's pod rows, priorities, groups, staged outputs and per-(pod, tile) records on the device (one
+    // buffer, grown on demand) and the pinned host block its inputs pass through
+    void *pre_mem = nullptr;
+    size_t pre_bytes = 0;
+    void *pre_host = nullptr;
     // kg_unreserve: the call's grouped entries on the device and the pinned block they pass through (both grown on
     // demand), the zone count of every node's row (host mirror of kg_node_row.n_zones, which no commit changes: the
     // zone arguments are validated before anything is launched) and the caller index → device slot map of kg_rsv_set
@@ -5131,6 +5423,9 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->diag_host) (void)hipHostFree(e->diag_host);
     if (e->cand_mem) (void)hipFree(e->cand_mem);
     if (e->cand_host) (void)hipHostFree(e->cand_host);
+    if (e->bound_mem) (void)hipFree(e->bound_mem);
+    if (e->pre_mem) (void)hipFree(e->pre_mem);
+    if (e->pre_host) (void)hipHostFree(e->pre_host);
     if (e->unr_mem) (void)hipFree(e->unr_mem);
     if (e->unr_host) (void)hipHostFree(e->unr_host);
     if (e->hot_lax) (void)hipFree(e->hot_lax);
@@ -5243,6 +5538,11 @@ kg_status kg_snapshot_reset(kg_engine *e, int32_t n_nodes) {
     e->pl.elig = nullptr;
     e->pl.elig_cnt = nullptr;
     e->pl.elig_stride = e->pl.elig_classes = 0;
+    if (e->bound_mem) HIP_TRY(e, hipFree(e->bound_mem));  // the bound-pod table refers to node indices: dropped
+    e->bound_mem = nullptr;
+    e->bound_tab = nullptr;
+    e->bound_count = e->bound_npre = e->bound_minprio = nullptr;
+    e->bound_max = 0;
     e->pl.cap = cap;
     e->n_nodes = n_nodes;
     e->node_bind_facts.assign((size_t)n_nodes, 0);
@@ -7178,6 +7478,298 @@ kg_status kg_candidates(kg_engine *e, const kg_pod_row *pods, int32_t n, int64_t
         if (n_feasible) HIP_TRY(e, hipMemcpyAsync(n_feasible, nf_d, nf_b, hipMemcpyDeviceToHost, e->stream));
     }
     HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the pinned pod rows are free for the next call)
+    return bounds_verdict(e);
+}
+
+// ---- the bound-pod table (kg_bound_set / _update / _download) and kg_preempt ------------------------------------
+namespace {
+// one list entry as the table holds it (KG_BOUND_FIELDS words; BoundSrc reads them)
+void bound_pack(const kg_pod_row &r, int32_t prio, int64_t start_ns, int32_t pos, int64_t *out) {
+    for (int q = 0; q < KG_NUM_RES; q++) {
+        out[q] = r.request[q];
+        out[KG_BF_NUMA + q] = r.numa_request[q];
+    }
+    out[KG_BF_NONZERO] = r.nonzero_request[0];
+    out[KG_BF_NONZERO + 1] = r.nonzero_request[1];
+    out[KG_BF_START] = start_ns;
+    const uint64_t hi = (uint64_t)(uint32_t)pos | ((r.flags & KG_POD_NON_PREEMPTIBLE) ? 0x100ull : 0ull);
+    out[KG_BF_META] = (int64_t)((uint64_t)(uint32_t)prio | (hi << 32));
+    const uint64_t keys = (uint64_t)(r.request_present & 0xFFFu) | ((uint64_t)(r.numa_request_present & 0xFFFu) << 12);
+    out[KG_BF_KEYS] = (int64_t)((uint64_t)(uint32_t)r.quota | (keys << 32));
+}
+void bound_unpack(const int64_t *in, kg_pod_row &r, int32_t &prio, int64_t &start_ns, int32_t &pos) {
+    memset(&r, 0, sizeof(r));
+    for (int q = 0; q < KG_NUM_RES; q++) {
+        r.request[q] = in[q];
+        r.numa_request[q] = in[KG_BF_NUMA + q];
+    }
+    r.nonzero_request[0] = in[KG_BF_NONZERO];
+    r.nonzero_request[1] = in[KG_BF_NONZERO + 1];
+    start_ns = in[KG_BF_START];
+    const uint64_t meta = (uint64_t)in[KG_BF_META], keys = (uint64_t)in[KG_BF_KEYS];
+    prio = (int32_t)(uint32_t)meta;
+    pos = (int32_t)((meta >> 32) & 0xFFull);
+    r.flags = ((meta >> 40) & 1ull) ? KG_POD_NON_PREEMPTIBLE : 0u;
+    r.quota = (int32_t)(uint32_t)keys;
+    r.request_present = (uint32_t)(keys >> 32) & 0xFFFu;
+    r.numa_request_present = (uint32_t)(keys >> 44) & 0xFFFu;
+}
+// the summary of one list: its preemptible pods and their lowest priority
+void bound_summary(const kg_pod_row *rows, const int32_t *prio, int32_t n, int32_t &pre, int32_t &minp) {
+    pre = 0;
+    minp = INT32_MAX;
+    for (int32_t i = 0; i < n; i++)
+        if (!(rows[i].flags & KG_POD_NON_PREEMPTIBLE)) {
+            pre++;
+            if (prio[i] < minp) minp = prio[i];
+        }
+}
+}  // namespace
+
+kg_status kg_bound_set(kg_engine *e, const int32_t *first, const kg_pod_row *rows, const int32_t *priority,
+                       const int64_t *start_ns, int32_t max_per_node) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (!first) return set_err(e, KG_ERR_INVALID_ARG, "null offsets");
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised (kg_snapshot_reset)");
+    if (max_per_node < 1 || max_per_node > KG_BOUND_MAX_PER_NODE)
+        return set_err(e, KG_ERR_RANGE, "max_per_node %d outside 1..%d", max_per_node, KG_BOUND_MAX_PER_NODE);
+    const int64_t N = e->n_nodes, cap = e->pl.cap;
+    if (first[0] != 0) return set_err(e, KG_ERR_RANGE, "offsets do not start at 0");
+    for (int64_t j = 0; j < N; j++) {
+        if (first[j + 1] < first[j]) return set_err(e, KG_ERR_RANGE, "node %lld: offsets do not rise", (long long)j);
+        if (first[j + 1] - first[j] > max_per_node)
+            return set_err(e, KG_ERR_RANGE, "node %lld: %d bound pods, max_per_node %d", (long long)j, first[j + 1] - first[j], max_per_node);
+    }
+    const int64_t total = first[N];
+    if (total > 0 && (!rows || !priority || !start_ns)) return set_err(e, KG_ERR_INVALID_ARG, "null rows, priority or start_ns");
+    for (int64_t i = 0; i < total; i++)
+        if (!kg_pod_row_in_bounds(rows[i])) return set_err(e, KG_ERR_RANGE, "bound pod %lld: request outside the engine bounds", (long long)i);
+    const size_t tab_n = (size_t)max_per_node * KG_BOUND_FIELDS * (size_t)cap;
+    std::vector<int64_t> tab(tab_n, 0);
+    std::vector<int32_t> sum(3 * (size_t)cap, 0);
+    int32_t order[KG_BOUND_MAX_PER_NODE];
+    int64_t rec[KG_BOUND_FIELDS];
+    for (int64_t j = 0; j < cap; j++) sum[2 * (size_t)cap + (size_t)j] = INT32_MAX;
+    for (int64_t j = 0; j < N; j++) {
+        const int32_t b = first[j], n = first[j + 1] - b;
+        kg_bound_order(priority + b, start_ns + b, n, order);
+        for (int32_t s = 0; s < n; s++) {
+            bound_pack(rows[b + order[s]], priority[b + order[s]], start_ns[b + order[s]], order[s], rec);
+            for (int f = 0; f < KG_BOUND_FIELDS; f++) tab[((size_t)s * KG_BOUND_FIELDS + (size_t)f) * (size_t)cap + (size_t)j] = rec[f];
+        }
+        int32_t pre, minp;
+        bound_summary(rows + b, priority + b, n, pre, minp);
+        sum[(size_t)j] = n;
+        sum[(size_t)cap + (size_t)j] = pre;
+        sum[2 * (size_t)cap + (size_t)j] = minp;
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // evaluations in flight finish first
+    if (e->eval_stream) HIP_TRY(e, hipStreamSynchronize(e->eval_stream));
+    if (e->bound_mem) HIP_TRY(e, hipFree(e->bound_mem));
+    e->bound_mem = nullptr;
+    e->bound_tab = nullptr;
+    e->bound_count = e->bound_npre = e->bound_minprio = nullptr;
+    e->bound_max = 0;
+    const size_t tab_b = (tab_n * 8 + 255) / 256 * 256, sum_b = sum.size() * 4;
+    HIP_TRY(e, hipMalloc(&e->bound_mem, tab_b + sum_b));
+    HIP_TRY(e, h2d(e, e->bound_mem, tab.data(), tab_n * 8, e->stream));
+    HIP_TRY(e, h2d(e, (char *)e->bound_mem + tab_b, sum.data(), sum_b, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the host images go out of scope)
+    e->bound_tab = (int64_t *)e->bound_mem;
+    e->bound_count = (int32_t *)((char *)e->bound_mem + tab_b);
+    e->bound_npre = e->bound_count + cap;
+    e->bound_minprio = e->bound_npre + cap;
+    e->bound_max = max_per_node;
+    return KG_OK;
+}
+
+kg_status kg_bound_update(kg_engine *e, int32_t node, const kg_pod_row *rows, const int32_t *priority,
+                          const int64_t *start_ns, int32_t n) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised (kg_snapshot_reset)");
+    if (!e->bound_mem) return set_err(e, KG_ERR_STATE, "no bound-pod table (kg_bound_set)");
+    if (node < 0 || node >= e->n_nodes) return set_err(e, KG_ERR_RANGE, "node %d outside the snapshot", node);
+    if (n < 0 || n > e->bound_max) return set_err(e, KG_ERR_RANGE, "%d bound pods, the table keeps %d per node", n, e->bound_max);
+    if (n > 0 && (!rows || !priority || !start_ns)) return set_err(e, KG_ERR_INVALID_ARG, "null rows, priority or start_ns");
+    for (int32_t i = 0; i < n; i++)
+        if (!kg_pod_row_in_bounds(rows[i])) return set_err(e, KG_ERR_RANGE, "bound pod %d: request outside the engine bounds", i);
+    int32_t order[KG_BOUND_MAX_PER_NODE];
+    kg_bound_order(priority, start_ns, n, order);
+    std::vector<int64_t> staged((size_t)(n > 0 ? n : 1) * KG_BOUND_FIELDS, 0);
+    for (int32_t s = 0; s < n; s++)
+        bound_pack(rows[order[s]], priority[order[s]], start_ns[order[s]], order[s], staged.data() + (size_t)s * KG_BOUND_FIELDS);
+    int32_t pre, minp;
+    bound_summary(rows, priority, n, pre, minp);
+    const size_t sb = staged.size() * 8;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // evaluations in flight finish first
+    if (e->eval_stream) HIP_TRY(e, hipStreamSynchronize(e->eval_stream));
+    st = ensure_scratch(e, sb + 256);
+    if (st) return st;
+    HIP_TRY(e, h2d(e, e->scratch, staged.data(), sb, e->stream));
+    const int threads = n * KG_BOUND_FIELDS > 0 ? n * KG_BOUND_FIELDS : 1;
+    hipLaunchKernelGGL(k_bound_update, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream, e->bound_tab,
+                       e->bound_count, e->bound_npre, e->bound_minprio, e->pl.cap, e->bound_max, (int64_t)node,
+                       (const int64_t *)e->scratch, n, pre, minp);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // staging buffer reuse
+    return bounds_verdict(e);
+}
+
+kg_status kg_bound_download(kg_engine *e, int32_t node, kg_pod_row *rows, int32_t *priority, int64_t *start_ns,
+                            int32_t cap, int32_t *n) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (!n) return set_err(e, KG_ERR_INVALID_ARG, "null count");
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised (kg_snapshot_reset)");
+    if (!e->bound_mem) return set_err(e, KG_ERR_STATE, "no bound-pod table (kg_bound_set)");
+    if (node < 0 || node >= e->n_nodes) return set_err(e, KG_ERR_RANGE, "node %d outside the snapshot", node);
+    if (cap < 0 || cap > e->bound_max) return set_err(e, KG_ERR_RANGE, "capacity %d, the table keeps %d per node", cap, e->bound_max);
+    if (cap > 0 && (!rows || !priority || !start_ns)) return set_err(e, KG_ERR_INVALID_ARG, "null rows, priority or start_ns");
+    int32_t have = 0;
+    HIP_TRY(e, hipMemcpyAsync(&have, e->bound_count + node, 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    *n = have;
+    if (have > cap) return set_err(e, KG_ERR_RANGE, "node %d holds %d bound pods, capacity %d", node, have, cap);
+    if (have == 0) return KG_OK;
+    // the node's column: one 8-byte element per (slot, field), a table row apart
+    std::vector<int64_t> col((size_t)have * KG_BOUND_FIELDS);
+    HIP_TRY(e, hipMemcpy2DAsync(col.data(), 8, e->bound_tab + node, (size_t)e->pl.cap * 8, 8, (size_t)have * KG_BOUND_FIELDS,
+                                hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    for (int32_t s = 0; s < have; s++) {
+        kg_pod_row r;
+        int32_t prio, pos;
+        int64_t t;
+        bound_unpack(col.data() + (size_t)s * KG_BOUND_FIELDS, r, prio, t, pos);
+        if (pos < 0 || pos >= have) return set_err(e, KG_ERR_STATE, "node %d: slot %d names position %d of %d", node, s, pos, have);
+        rows[pos] = r;
+        priority[pos] = prio;
+        start_ns[pos] = t;
+    }
+    return KG_OK;
+}
+
+// The dry run of n preemptors over the shard: k_preempt (the optional plane, per-(pod, tile) best records) and
+// k_preempt_pick (the pick over the tiles), then one stream synchronisation.  Like kg_diagnose the pod rows travel with
+// the call and nothing of the engine's state is touched.
+kg_status kg_preempt(kg_engine *e, const kg_pod_row *pods, const int32_t *priority, int32_t n, int64_t now_ns, uint32_t flags,
+                     int64_t *pick, uint32_t *plane, int32_t out_on_device) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (flags != 0) return set_err(e, KG_ERR_INVALID_ARG, "unknown kg_preempt flags 0x%x", flags);
+    if (n < 0 || (n > 0 && (!pods || !priority || !pick))) return set_err(e, KG_ERR_INVALID_ARG, "null pods, priority or pick");
+    if (n > KG_PREEMPT_MAX_PODS) return set_err(e, KG_ERR_RANGE, "kg_preempt takes at most %d pods (got %d)", KG_PREEMPT_MAX_PODS, n);
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised");
+    const uint32_t plug = e->cfg.enabled_plugins;
+    for (int32_t i = 0; i < n; i++) {
+        const kg_pod_row &pod = pods[i];
+        if (!kg_pod_row_in_bounds(pod)) return set_err(e, KG_ERR_RANGE, "pod %d: request outside the engine bounds", i);
+        if (pod.elig_class < 0 || pod.elig_class > e->pl.elig_classes)
+            return set_err(e, KG_ERR_RANGE, "pod %d: elig_class %d outside the loaded eligibility classes (have %d: kg_elig_set)",
+                           i, pod.elig_class, e->pl.elig_classes);
+    }
+    // what the dry run does not answer
+    if (plug & KG_PLUGIN_NUMA)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_preempt under NodeNUMAResource (its verdict moves with NodeInfo.Requested)");
+    if ((plug & KG_PLUGIN_RESERVATION) && e->n_rn > 0)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_preempt with reservation slots loaded (Reservation's own AddPod / RemovePod)");
+    if (!e->bound_mem) return set_err(e, KG_ERR_STATE, "no bound-pod table (kg_bound_set)");
+    for (int32_t i = 0; i < n; i++)
+        if ((plug & KG_PLUGIN_ELASTICQUOTA) && pods[i].quota >= e->n_quota)
+            return set_err(e, KG_ERR_STATE, "pod %d: quota index %d without a kg_quota_set group (have %d)", i, pods[i].quota,
+                           e->n_quota);
+    if (n == 0) return KG_OK;
+    const bool dev = out_on_device != 0;
+    const int64_t width = e->shard_end - e->shard_begin;
+    const int64_t words = (width + 63) / 64, stride = words * 64;
+    const size_t pick_b = (size_t)n * KG_PREEMPT_PICK_WORDS * 8, plane_b = (size_t)n * (size_t)stride * 4;
+    const size_t out_b = pick_b + (plane ? plane_b : 0);
+    if (width <= 0) {   // an empty shard: no candidate anywhere, nothing to launch
+        std::vector<int64_t> none((size_t)n * KG_PREEMPT_PICK_WORDS, 0);
+        for (int32_t i = 0; i < n; i++) none[(size_t)i * KG_PREEMPT_PICK_WORDS] = -1;
+        if (dev) {
+            HIP_TRY(e, hipMemcpyAsync(pick, none.data(), pick_b, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(e, hipStreamSynchronize(e->stream));
+        } else {
+            memcpy(pick, none.data(), pick_b);
+        }
+        e->ctr.eval_calls++;
+        e->ctr.out_bytes += out_b;
+        return KG_OK;
+    }
+    const int64_t tile_begin = e->shard_begin / KG_TILE;
+    const int64_t shard_tiles = (e->shard_end + KG_TILE - 1) / KG_TILE - tile_begin;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t pods_b = sizeof(kg_pod_dev) * (size_t)n, i32_b = 4 * (size_t)n;
+    const size_t slab_b = (size_t)n * (size_t)shard_tiles * 8 * 8;
+    const size_t in_b = up(pods_b) + 2 * up(i32_b);
+    const size_t need = in_b + up(pick_b) + up(slab_b);
+    if (e->pre_bytes < need) {
+        if (e->pre_mem) HIP_TRY(e, hipFree(e->pre_mem));
+        e->pre_mem = nullptr;
+        e->pre_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->pre_mem, need));
+        e->pre_bytes = need;
+    }
+    if (!e->pre_host)
+        HIP_TRY(e, hipHostMalloc(&e->pre_host, up(sizeof(kg_pod_dev) * KG_PREEMPT_MAX_PODS) + 2 * up(4 * KG_PREEMPT_MAX_PODS),
+                                 hipHostMallocDefault));
+    uint32_t *plane_d = nullptr;
+    if (plane && dev) {
+        plane_d = plane;
+    } else if (plane) {   // a host plane: staged in scratch, copied back ahead of the synchronisation
+        st = ensure_scratch(e, plane_b + 256);
+        if (st) return st;
+        plane_d = (uint32_t *)e->scratch;
+    }
+    e->ctr.eval_calls++;
+    e->ctr.evals += (uint64_t)n * (uint64_t)width;
+    e->ctr.out_bytes += out_b;
+    char *m = (char *)e->pre_mem, *h = (char *)e->pre_host;
+    kg_pod_dev *pods_h = (kg_pod_dev *)h;
+    int32_t *prio_h = (int32_t *)(h + up(pods_b)), *grp_h = (int32_t *)(h + up(pods_b) + up(i32_b));
+    for (int32_t i = 0; i < n; i++) {
+        kg_pod_dev_from_row(e->cfg, pods[i], pods_h[i]);
+        prio_h[i] = priority[i];
+        grp_h[i] = pods[i].quota;   // the row's own group: canPreempt compares it with ElasticQuota off too
+    }
+    HIP_TRY(e, h2d(e, m, h, in_b, e->stream));
+    const kg_pod_dev *pods_d = (const kg_pod_dev *)m;
+    const int32_t *prio_d = (const int32_t *)(m + up(pods_b)), *grp_d = (const int32_t *)(m + up(pods_b) + up(i32_b));
+    int64_t *pick_d = dev ? pick : (int64_t *)(m + in_b);
+    int64_t *slab = (int64_t *)(m + in_b + up(pick_b));
+    PreArgs a{};
+    a.node_end = e->shard_end;
+    a.col_begin = e->shard_begin;
+    a.stride = stride;
+    a.now_ns = now_ns;
+    a.tile_begin = (int32_t)tile_begin;
+    a.shard_tiles = (int32_t)shard_tiles;
+    // pods per workgroup: whole LDS passes; a tile's nodes are loaded once per workgroup, so few groups
+    int64_t ppg = ((int64_t)n * shard_tiles + 2047) / 2048;
+    ppg = (ppg + KG_SPILL_CHUNK - 1) / KG_SPILL_CHUNK * KG_SPILL_CHUNK;
+    if (ppg < KG_SPILL_CHUNK) ppg = KG_SPILL_CHUNK;
+    const int64_t groups = (n + ppg - 1) / ppg;
+    const int64_t blocks = (shard_tiles + KG_XCDS - 1) / KG_XCDS * KG_XCDS * groups;
+    a.n_groups = (int32_t)groups;
+    a.pods_per_group = (int32_t)ppg;
+    a.n_pods = n;
+    a.n_quota = e->n_quota;
+    a.quota = (plug & KG_PLUGIN_ELASTICQUOTA) ? (const kg_quota *)e->quota : (const kg_quota *)nullptr;
+    a.bt = BoundTab{e->bound_tab, e->bound_count, e->bound_npre, e->bound_minprio, e->pl.cap, e->bound_max};
+    hipLaunchKernelGGL(plane_d ? k_preempt<true> : k_preempt<false>, dim3((unsigned)blocks), dim3(KG_BLOCK), 0, e->stream,
+                       e->consts, e->pl, a, pods_d, prio_d, grp_d, plane_d, slab);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(k_preempt_pick, dim3((unsigned)n), dim3(64), 0, e->stream, (const int64_t *)slab, n, (int32_t)shard_tiles,
+                       pick_d);
+    HIP_TRY(e, hipGetLastError());
+    if (!dev) {
+        HIP_TRY(e, hipMemcpyAsync(pick, pick_d, pick_b, hipMemcpyDeviceToHost, e->stream));
+        if (plane) HIP_TRY(e, hipMemcpyAsync(plane, plane_d, plane_b, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the pinned inputs are free for the next call)
     return bounds_verdict(e);
 }
 

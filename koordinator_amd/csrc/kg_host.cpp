@@ -883,9 +883,109 @@ kg_status kg_row_rsv_restore(const kg_config *cfg, const kg_node_row *node, cons
     return KG_OK;
 }
 
+// The preemption dry run of one pair on host rows through kg_preempt_pair, the routine k_preempt runs per lane: the
+// bound list is read in importance order through a sorted index; like kg_row_why no engine and no eligibility class.
+namespace {
+struct RowBoundSrc {
+    const kg_pod_row *rows;
+    const int32_t *prio;
+    const int64_t *start;
+    const int32_t *order;
+    int64_t req(int s, int r) const { return rows[order[s]].request[r]; }
+    int64_t numa_req(int s, int r) const { return rows[order[s]].numa_request[r]; }
+    uint32_t numa_present(int s) const { return rows[order[s]].numa_request_present; }
+    bool non_preemptible(int s) const { return (rows[order[s]].flags & KG_POD_NON_PREEMPTIBLE) != 0; }
+    int32_t quota(int s) const { return rows[order[s]].quota; }
+    int32_t priority(int s) const { return prio[order[s]]; }
+    int64_t start_ns(int s) const { return start[order[s]]; }
+    int position(int s) const { return order[s]; }
+};
+}  // namespace
+
+kg_status kg_row_preempt(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *bound, const int32_t *bound_priority,
+                         const int64_t *bound_start_ns, int32_t n_bound, const kg_pod_row *pod, int32_t pod_priority,
+                         const kg_quota *quotas, int32_t n_quotas, int64_t now_ns, int32_t *status, uint64_t victims[2],
+                         int64_t stats[4]) {
+    if (!cfg || !node || !pod || !status || !victims || !stats) return KG_ERR_INVALID_ARG;
+    if (n_bound < 0 || n_bound > KG_BOUND_MAX_PER_NODE) return KG_ERR_RANGE;
+    if (n_bound > 0 && (!bound || !bound_priority || !bound_start_ns)) return KG_ERR_INVALID_ARG;
+    if (n_quotas < 0 || (n_quotas > 0 && !quotas)) return KG_ERR_INVALID_ARG;
+    if (cfg->enabled_plugins & KG_PLUGIN_NUMA) return KG_ERR_UNSUPPORTED;
+    const bool q_on = (cfg->enabled_plugins & KG_PLUGIN_ELASTICQUOTA) && pod->quota >= 0;
+    if (q_on && pod->quota >= n_quotas) return KG_ERR_RANGE;
+    kg_consts k;
+    kg_consts_from_config(*cfg, k);
+    kg_pod_dev pd;
+    kg_pod_dev_from_row(*cfg, *pod, pd);
+    // one-node planes, only for the derived flags; every part of the verdict but NodeResourcesFit, once
+    kg_node_row row = *node;
+    int64_t free_[KG_NUM_RES], metric_ns;
+    double fit_R[KG_NUM_RES], fit_F[KG_NUM_RES], la_R[2], la_F[4];
+    uint32_t dflags, fmask;
+    kg_planes pl{&row, free_, fit_R, fit_F, la_R, la_F, &metric_ns, &dflags, &fmask, 1};
+    kg_finalize_node(k, pl, 0);
+    const bool valid = (row.flags & KG_NODE_VALID) != 0;
+    const bool rest_ok = (kg_pair_why<false>(k, row, dflags, pd, now_ns, 0) & ~KG_WHY_FIT_MASK) == 0;
+    kg_pre_state st;
+    kg_pre_quota q;
+    memset(&q, 0, sizeof(q));
+    for (int r = 0; r < KG_NUM_RES; r++) {
+        st.free_[r] = row.alloc[r] - row.requested[r];
+        st.used[r] = q_on ? kg_rl_get(quotas[pod->quota].used, r) : 0;
+        if (q_on) q.limit[r] = quotas[pod->quota].used_limit.v[r];
+    }
+    st.pod_count = row.pod_count;
+    if (q_on) {
+        q.mask = quotas[pod->quota].used_limit.present & pd.numa_present & ((1u << KG_NUM_RES) - 1u);
+        q.active = 1;
+    }
+    int32_t order[KG_BOUND_MAX_PER_NODE];
+    kg_bound_order(bound_priority, bound_start_ns, n_bound, order);
+    const RowBoundSrc src{bound, bound_priority, bound_start_ns, order};
+    kg_pre_out o;
+    kg_preempt_pair(k, pd, pod_priority, pod->quota, valid, rest_ok, row.allowed_pods, st, q, src, n_bound, o);
+    *status = o.status;
+    const bool cand = o.status == KG_PRE_CANDIDATE;
+    victims[0] = cand ? o.victims[0] : 0;
+    victims[1] = cand ? o.victims[1] : 0;
+    stats[0] = cand ? o.n_victims : 0;
+    stats[1] = cand ? o.hi_prio : 0;
+    stats[2] = cand ? o.prio_sum : 0;
+    stats[3] = cand ? o.earliest_ns : 0;
+    return KG_OK;
+}
+
+// kg_preempt_merge (koord_gpu.h): the picks of several shards or ranks for the same pods, the better one by
+// kg_pre_better (the order k_preempt_pick applies over the tiles), the candidate counts summed.
+kg_status kg_preempt_merge(const int64_t *picks, int32_t n_lists, int32_t n, int64_t *out) {
+    if (n_lists < 1 || n < 0 || !picks || !out) return KG_ERR_INVALID_ARG;
+    constexpr int W = KG_PREEMPT_PICK_WORDS;
+    for (int32_t p = 0; p < n; p++) {
+        int64_t best[W] = {-1, 0, 0, 0, 0, 0, 0, 0};
+        int64_t cands = 0;
+        for (int32_t l = 0; l < n_lists; l++) {
+            const int64_t *c = picks + ((size_t)l * (size_t)n + (size_t)p) * W;
+            cands += c[7];
+            if (kg_pre_better(c[0], c[1], c[2], c[3], c[4], best[0], best[1], best[2], best[3], best[4]))
+                for (int w = 0; w < W; w++) best[w] = c[w];
+        }
+        best[7] = best[0] < 0 ? 0 : cands;
+        for (int w = 0; w < W; w++) out[(size_t)p * W + w] = best[w];
+    }
+    return KG_OK;
+}
+
 }  // extern "C"
 
 // ---- engine-internal helpers shared with kg_engine.hip ------------------------------------
+
+void kg_bound_order(const int32_t *priority, const int64_t *start_ns, int32_t n, int32_t *order) {
+    for (int32_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order, order + n, [&](int32_t a, int32_t b) {
+        if (priority[a] != priority[b]) return priority[a] > priority[b];
+        return start_ns[a] < start_ns[b];
+    });
+}
 
 void kg_consts_from_config(const kg_config &c, kg_consts &k) {
     memset(&k, 0, sizeof(k));

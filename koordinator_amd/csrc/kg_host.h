@@ -10,6 +10,9 @@ bool kg_pod_row_in_bounds(const kg_pod_row &row);
 // one entry's zone_release ([KG_MAX_ZONES][2]) against the node's zone count (kg_row_unreserve, kg_unreserve)
 bool kg_zone_release_ok(const int64_t *rel, int32_t n_zones);
 int kg_numa_list_count(const kg_pod_row &row);   // NodeNUMAResource hint lists the pod can produce
+// util.MoreImportantPod order of one node's bound list (kg_row_preempt, kg_bound_set): order[s] = the caller position of
+// the s-th most important pod - higher priority first, then the earlier start, ties in the caller's order
+void kg_bound_order(const int32_t *priority, const int64_t *start_ns, int32_t n, int32_t *order);
 // Fills the S-slot hot row (slot s ↔ resource slot_res[s]) and returns the pod's resources that
 // need a slot (compared or scored), so the caller can check the profile covers them.
 template <int S>

@@ -88,6 +88,46 @@ def row_why(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray, now_ns: 
     return int(w.value)
 
 
+def row_preempt(cfg: np.ndarray, node_row: np.ndarray, bound_rows: np.ndarray, bound_priority, bound_start_ns,
+                pod_row: np.ndarray, pod_priority: int, now_ns: int, quotas: Optional[np.ndarray] = None) -> dict:
+    """kg_row_preempt: the preemption dry run of one (preemptor, node) pair on host rows (SelectVictimsOnNode without
+    PodDisruptionBudgets).  `bound_rows` / `bound_priority` / `bound_start_ns`: the node's bound pods in the caller's
+    order.  Returns status (nat.PRE_*), victims (bool [nat.BOUND_MAX_PER_NODE], caller positions), n_victims, hi_prio,
+    prio_sum and earliest_ns; everything but the status is zero unless the status is nat.PRE_CANDIDATE.  Ignores
+    elig_class."""
+    rows = np.ascontiguousarray(bound_rows, dtype=nat.POD_ROW).reshape(-1)
+    n = len(rows)
+    pr = np.ascontiguousarray(bound_priority, dtype=np.int32).reshape(-1)
+    ts = np.ascontiguousarray(bound_start_ns, dtype=np.int64).reshape(-1)
+    if len(pr) != n or len(ts) != n:
+        raise ValueError("row_preempt takes one priority and one start time per bound row")
+    q = None if quotas is None else np.ascontiguousarray(quotas, dtype=nat.QUOTA).reshape(-1)
+    status = ctypes.c_int32(0)
+    mask = np.zeros(2, dtype=np.uint64)
+    stats = np.zeros(4, dtype=np.int64)
+    _check(nat.lib().kg_row_preempt(nat.ptr(cfg), nat.ptr(node_row), nat.ptr(rows) if n else None, nat.ptr(pr) if n else None,
+                                    nat.ptr(ts) if n else None, n, nat.ptr(pod_row), int(pod_priority),
+                                    nat.ptr(q) if q is not None and len(q) else None, 0 if q is None else len(q),
+                                    int(now_ns), ctypes.byref(status), nat.ptr(mask), nat.ptr(stats)), what="kg_row_preempt")
+    return {"status": int(status.value), "victims": unpack_victims(mask), "n_victims": int(stats[0]),
+            "hi_prio": int(stats[1]), "prio_sum": int(stats[2]), "earliest_ns": int(stats[3])}
+
+
+def unpack_victims(words: np.ndarray) -> np.ndarray:
+    """Victim mask words uint64 [..., 2] -> bool [..., nat.BOUND_MAX_PER_NODE] (bit b: position b of the node's list)."""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    bits = np.unpackbits(w.view(np.uint8).reshape(*w.shape[:-1], 16), axis=-1, bitorder="little")
+    return bits.astype(bool)
+
+
+def _pick_dict(pick: np.ndarray) -> dict:
+    """kg_preempt's pick words int64 [n][8] as named arrays."""
+    pick = np.ascontiguousarray(pick, dtype=np.int64).reshape(-1, nat.PREEMPT_PICK_WORDS)
+    return {"node": pick[:, 0].astype(np.int32), "victims": unpack_victims(pick[:, 5:7].view(np.uint64)),
+            "n_victims": pick[:, 1].astype(np.int32), "hi_prio": pick[:, 2].astype(np.int32), "prio_sum": pick[:, 3].copy(),
+            "earliest_ns": pick[:, 4].copy(), "n_candidates": pick[:, 7].astype(np.int32), "pick": pick}
+
+
 # the reference's reason strings: upstream NodeResourcesFit ("Too many pods", "Insufficient <resource>"),
 # LoadAwareScheduling (load_aware.go:45, resource not named: the word holds the plugin's verdict alone) and
 # NodeNUMAResource (frameworkext/topologymanager/manager.go:70)
@@ -605,6 +645,82 @@ class Engine:
         _check(nat.lib().kg_candidates(self._h, nat.ptr(rows), len(rows), int(now_ns), int(k), 0, keys_ptr or None,
                                        scores_ptr or None, n_feasible_ptr or None, 1), self, "kg_candidates")
 
+    # preemption dry run ---------------------------------------------------------------------
+    def set_bound_pods(self, first, rows: np.ndarray, priority, start_ns, max_per_node: int = nat.BOUND_MAX_PER_NODE) -> None:
+        """kg_bound_set: replace the bound-pod table (NodeInfo.Pods of every snapshot node).  `first`: int32
+        [n_nodes + 1] CSR offsets into `rows` (POD_ROW), `priority` (int32) and `start_ns` (int64,
+        nat.START_NS_NONE for a pod without a start time); `max_per_node`: the slots kept per node (1..128)."""
+        first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        if len(first) != self.n_nodes + 1:
+            raise ValueError("set_bound_pods takes n_nodes + 1 offsets")
+        rows = np.ascontiguousarray(rows, dtype=nat.POD_ROW).reshape(-1)
+        pr = np.ascontiguousarray(priority, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(start_ns, dtype=np.int64).reshape(-1)
+        if len(pr) != len(rows) or len(ts) != len(rows):
+            raise ValueError("set_bound_pods takes one priority and one start time per row")
+        n = len(rows)
+        _check(nat.lib().kg_bound_set(self._h, nat.ptr(first), nat.ptr(rows) if n else None, nat.ptr(pr) if n else None,
+                                      nat.ptr(ts) if n else None, int(max_per_node)), self, "kg_bound_set")
+        self.bound_max = int(max_per_node)
+
+    def update_bound_pods(self, node: int, rows: np.ndarray, priority, start_ns) -> None:
+        """kg_bound_update: replace one node's list (empty arrays empty it).  The caller keeps the table in step with
+        its pod events this way: place() / commit() / unreserve() do not touch it."""
+        rows = np.ascontiguousarray(rows, dtype=nat.POD_ROW).reshape(-1)
+        pr = np.ascontiguousarray(priority, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(start_ns, dtype=np.int64).reshape(-1)
+        if len(pr) != len(rows) or len(ts) != len(rows):
+            raise ValueError("update_bound_pods takes one priority and one start time per row")
+        n = len(rows)
+        _check(nat.lib().kg_bound_update(self._h, int(node), nat.ptr(rows) if n else None, nat.ptr(pr) if n else None,
+                                         nat.ptr(ts) if n else None, n), self, "kg_bound_update")
+
+    def download_bound_pods(self, node: int):
+        """kg_bound_download: (rows, priority, start_ns) of one node's list in the caller's order.  A row carries the
+        fields the table keeps (request, request_present, nonzero_request, numa_request, numa_request_present, quota,
+        flags & POD_NON_PREEMPTIBLE); the others are zero."""
+        cap = int(getattr(self, "bound_max", nat.BOUND_MAX_PER_NODE))
+        rows = np.zeros(cap, dtype=nat.POD_ROW)
+        pr = np.zeros(cap, dtype=np.int32)
+        ts = np.zeros(cap, dtype=np.int64)
+        n = ctypes.c_int32(0)
+        _check(nat.lib().kg_bound_download(self._h, int(node), nat.ptr(rows), nat.ptr(pr), nat.ptr(ts), cap,
+                                           ctypes.byref(n)), self, "kg_bound_download")
+        return rows[:n.value].copy(), pr[:n.value].copy(), ts[:n.value].copy()
+
+    def preempt(self, pod_rows: np.ndarray, priority, now_ns: int, plane: bool = False) -> dict:
+        """kg_preempt: the preemption dry run of the pods (at most nat.PREEMPT_MAX_PODS rows with their priorities; they
+        travel with the call, the batch of set_pods is not touched) against every node of the shard, and the node to
+        preempt on.  Returns node [n] i32 (-1: no candidate), victims [n][128] bool (positions in the picked node's
+        list), n_victims, hi_prio, prio_sum, earliest_ns, n_candidates and pick (the raw words, for merge_preempt);
+        with `plane` also status / n_victims_plane / n_potential [n][stride] (columns as eval()'s planes).  Mutates
+        nothing."""
+        rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+        n = len(rows)
+        pr = np.ascontiguousarray(priority, dtype=np.int32).reshape(-1)
+        if len(pr) != n:
+            raise ValueError("preempt takes one priority per pod row")
+        pick = np.zeros((n, nat.PREEMPT_PICK_WORDS), dtype=np.int64)
+        cells = np.zeros((n, self.score_stride), dtype=np.uint32) if plane else None
+        _check(nat.lib().kg_preempt(self._h, nat.ptr(rows) if n else None, nat.ptr(pr) if n else None, n, int(now_ns), 0,
+                                    nat.ptr(pick) if n else None,
+                                    nat.ptr(cells) if plane and cells.size else None, 0), self, "kg_preempt")
+        res = _pick_dict(pick)
+        if plane:
+            res["status"] = (cells & np.uint32(0xFF)).astype(np.uint8)
+            res["n_victims_plane"] = ((cells >> np.uint32(8)) & np.uint32(0xFF)).astype(np.uint8)
+            res["n_potential"] = ((cells >> np.uint32(16)) & np.uint32(0xFF)).astype(np.uint8)
+            res["plane"] = cells
+        return res
+
+    def preempt_device(self, pod_rows: np.ndarray, priority, now_ns: int, pick_ptr: int, plane_ptr: int = 0) -> None:
+        """kg_preempt into caller-owned device buffers (pick 8-byte aligned, the plane 16-byte aligned, any previous
+        content), as diagnose_device; the call returns after the launches completed."""
+        rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
+        pr = np.ascontiguousarray(priority, dtype=np.int32).reshape(-1)
+        _check(nat.lib().kg_preempt(self._h, nat.ptr(rows), nat.ptr(pr), len(rows), int(now_ns), 0, pick_ptr or None,
+                                    plane_ptr or None, 1), self, "kg_preempt")
+
     # Reservation / ElasticQuota -----------------------------------------------------------
     def set_reservations(self, rsv: np.ndarray) -> None:
         rsv = np.ascontiguousarray(rsv, dtype=nat.RESERVATION)
@@ -655,6 +771,18 @@ def merge_candidates(results: Sequence[dict]) -> dict:
     res["nodes"], res["totals"] = node.astype(np.int32), total
     res["n_feasible"] = np.sum([np.asarray(r["n_feasible"], dtype=np.uint32) for r in results], axis=0, dtype=np.uint32)
     return res
+
+
+def merge_preempt(results: Sequence[dict]) -> dict:
+    """kg_preempt_merge: the preempt() results of several ranks or shards for the same pods, combined on the host by
+    the pick order (ties to the lowest node index); n_candidates is the sum over the shards."""
+    if not results:
+        raise ValueError("merge_preempt takes at least one result")
+    picks = np.ascontiguousarray(np.stack([np.asarray(r["pick"], dtype=np.int64) for r in results]))
+    _, n, _ = picks.shape
+    out = np.zeros((n, nat.PREEMPT_PICK_WORDS), dtype=np.int64)
+    _check(nat.lib().kg_preempt_merge(nat.ptr(picks), len(results), n, nat.ptr(out)), what="kg_preempt_merge")
+    return _pick_dict(out)
 
 
 def pack_eligibility(masks: np.ndarray) -> np.ndarray:

@@ -241,16 +241,44 @@ class SnapshotFeeder:
         names = sorted(self.nodes, key=lambda n: self.index[n])
         return np.array([self.index[n] for n in names], dtype=np.int32), self._rows_for(names)
 
+    def _bound_for(self, names: List[str]):
+        """ingest.bound_pods over the named nodes (CSR offsets in the order of `names`): each node's bound,
+        non-terminated pods in UID order, which is their position (their identity in a victim mask) until the list
+        changes."""
+        uids = sorted(u for n in names for u in self.bound.get(n, ()))
+        cl = ingest.cluster_from_objects([self.nodes[n] for n in names], [self.pods[u] for u in uids],
+                                         now_ns=int(self.now_fn()))
+        return ingest.bound_pods(self.cfg, cl)
+
+    def bound_pods(self):
+        """(first, rows, priority, start_ns) of every node in row-index order for Engine.set_bound_pods (indices must
+        be dense, as for cluster()); flush() then keeps the engine's table in step."""
+        names = sorted(self.nodes, key=lambda n: self.index[n])
+        if [self.index[n] for n in names] != list(range(len(names))):
+            raise ValueError("row indices have holes (a deleted node's slot not refilled)")
+        return self._bound_for(names)
+
     def flush(self, eng: "_engine.Engine") -> int:
-        """Apply the pending deltas to an engine whose snapshot holds ≥ n_index rows — the changed rows and,
-        for a cpuset Reserve, the changed nodes' CPU tables (kg_cpus_set); returns rows written."""
+        """Apply the pending deltas to an engine whose snapshot holds ≥ n_index rows — the changed rows, for a cpuset
+        Reserve the changed nodes' CPU tables (kg_cpus_set) and, once the engine holds a bound-pod table
+        (Engine.set_bound_pods), the changed nodes' lists (kg_bound_update; a removed node's list is emptied);
+        returns rows written."""
         idx, rows, removed, view = self._take()
+        table = bool(getattr(eng, "bound_max", 0))
         for i in removed:
             if i not in set(idx.tolist()):
                 eng.remove(i)
+                if table:
+                    eng.update_bound_pods(i, np.zeros(0, dtype=nat.POD_ROW), [], [])
         if len(idx):
             eng.upsert(idx, rows)
             eng.set_cpus(view, np.arange(len(idx)), idx)
+            if table:
+                name_of = {i: n for n, i in self.index.items()}
+                first, b_rows, prio, start = self._bound_for([name_of[int(i)] for i in idx])
+                for k, i in enumerate(idx):
+                    lo, hi = int(first[k]), int(first[k + 1])
+                    eng.update_bound_pods(int(i), b_rows[lo:hi], prio[lo:hi], start[lo:hi])
         return len(idx)
 
     def cluster(self) -> "ingest.ob.Cluster":

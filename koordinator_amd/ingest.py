@@ -234,7 +234,8 @@ def pod_from_object(pod: dict) -> ob.Pod:
         cpu_exclusive=spec_ann["preferredCPUExclusivePolicy"],
         daemonset=any(o.get("kind") == "DaemonSet" and o.get("controller", False) for o in owners),
         terminated=status.get("phase") in ("Succeeded", "Failed"),
-        node_name=spec.get("nodeName", ""))
+        node_name=spec.get("nodeName", ""),
+        start_time_ns=parse_time_ns(status["startTime"]) if status.get("startTime") else None)
 
 
 def resource_spec(annotations: dict) -> dict:
@@ -562,3 +563,26 @@ def cluster_from_objects(nodes: Iterable[dict], pods: Iterable[dict] = (), node_
         for uid, ts in sorted(items.items(), key=lambda kv: kv[1]):
             cl.assign_at(node_name, by_uid[uid], ts)
     return cl
+
+
+def bound_pods(cfg, cluster: ob.Cluster):
+    """The bound-pod table of a cluster for Engine.set_bound_pods (NodeInfo.Pods of every node as the preemption dry
+    run reads it): (first, rows, priority, start_ns) - CSR offsets over cluster.nodes, the pod rows, PodPriority
+    (Spec.Priority, 0 when nil) and Status.StartTime in ns (nat.START_NS_NONE when nil).  A node's list holds the
+    lister pods whose node_name is the node's, in lister order; terminated pods are left out, as NodeInfo holds none."""
+    import numpy as np
+
+    from . import _native as nat
+    from . import engine
+    by_node: Dict[str, List[ob.Pod]] = {}
+    for p in cluster.lister_pods.values():
+        if p.node_name and not p.terminated:
+            by_node.setdefault(p.node_name, []).append(p)
+    flat = [p for n in cluster.nodes for p in by_node.get(n.name, [])]
+    first = np.zeros(len(cluster.nodes) + 1, dtype=np.int32)
+    first[1:] = np.cumsum([len(by_node.get(n.name, [])) for n in cluster.nodes])
+    view = cluster.view()
+    rows = engine.build_pod_rows(cfg, view, [view.pod_index(p) for p in flat])
+    priority = np.array([p.priority or 0 for p in flat], dtype=np.int32)
+    start_ns = np.array([nat.START_NS_NONE if p.start_time_ns is None else p.start_time_ns for p in flat], dtype=np.int64)
+    return first, rows, priority, start_ns

@@ -145,6 +145,7 @@ class Pod:
     daemonset: bool = False
     terminated: bool = False
     node_name: str = ""
+    start_time_ns: Optional[int] = None   # Status.StartTime as Unix ns (None: nil; the preemption order then takes Now())
 
     @property
     def key(self) -> str:
