@@ -45,6 +45,9 @@
  *   kg_preempt              ElasticQuota's PostFilter preemption (elasticquota/plugin.go:302-321): SelectVictimsOnNode
  *   / kg_row_preempt        (preempt.go:111-215) dry-run on ALL nodes (GetOffsetAndNumCandidates, preempt.go:43-45), and
  *   / kg_preempt_merge      upstream pickOneNodeForPreemption (k8s v1.24.15 framework/preemption/preemption.go)
+ *   kg_pdb_thresholds       filterPodsWithPDBViolation (preempt.go:217-267) folded into one threshold per bound pod, the
+ *   / kg_bound_pdb_set      engine's plane of them and the dry run's PDB form: violating victims reprieved first,
+ *   / kg_row_preempt_pdb    numViolatingVictim as the pick's second criterion
  *   kg_rsv_set              reservation cache feed (reservation/cache.go:249-269 forEachAvailableReservationOnNode,
  *                           frameworkext/reservation_info.go:200-300): per-node reservation slots for the
  *                           Reservation plugin's restore / Filter / Score / Reserve (reservation/transformer.go:49-291,
@@ -1098,8 +1101,10 @@ kg_status kg_bound_download(kg_engine *eng, int32_t node, kg_pod_row *rows, int3
  * kg_row_preempt is the host entry (no engine; it ignores kg_pod_row.elig_class, as kg_row_why): bound[n_bound] in the
  * caller's order, quotas NULL <=> none.  KG_ERR_INVALID_ARG for null pointers, KG_ERR_RANGE for n_bound outside
  * 0..KG_BOUND_MAX_PER_NODE or an active quota index at or past n_quotas, KG_ERR_UNSUPPORTED with KG_PLUGIN_NUMA.
- * Out of scope (a caller that needs one of these keeps the host path): PodDisruptionBudgets (a PDB that matches a
- * potential victim), nominated pods (RunFilterPluginsWithNominatedPods' add-back), PodEligibleToPreemptOthers (a host
+ * PodDisruptionBudgets are the PDB form below (kg_pdb_thresholds, kg_bound_pdb_set, kg_row_preempt_pdb); without
+ * thresholds every potential victim is non-violating.
+ * Out of scope (a caller that needs one of these keeps the host path): nominated pods
+ * (RunFilterPluginsWithNominatedPods' add-back), PodEligibleToPreemptOthers (a host
  * check on one node), extenders, the eviction itself (the feeders deliver its pod deletes), NodeNUMAResource
  * (filterAmplifiedCPUs reads NodeInfo.Requested, so its verdict moves with every removal) and Reservation with slots
  * loaded (AddPod / RemovePod of its own, reservation/plugin.go:254-300). */
@@ -1122,7 +1127,8 @@ kg_status kg_row_preempt(const kg_config *cfg, const kg_node_row *node, const kg
  *         earliest_ns, victim mask word 0, word 1, n_candidates (the KG_PRE_CANDIDATE nodes of the shard).  With node
  *         -1 every other word is 0.  The pick among the candidates restates upstream pickOneNodeForPreemption: a node
  *         with no victim wins outright, then the lowest hi_prio, the lowest prio_sum, the fewest victims, the latest
- *         earliest_ns, and last the lowest node index (upstream: map order; the project's tie rule).
+ *         earliest_ns, and last the lowest node index (upstream: map order; the project's tie rule).  With a PDB
+ *         threshold plane loaded (below) word 1 also carries n_violating << 32, the second pick criterion.
  *   plane [n][64 * W] uint32 (may be NULL): status | n_victims << 8 | n_potential << 16 per node, kg_diagnose's plane
  *         contract - W = ceil((E - B) / 64), column c <=> node B + c, pad columns unspecified, nothing outside
  *         [n][64 * W] written, a device pointer 16-byte aligned, no pre-zeroing needed.
@@ -1143,6 +1149,60 @@ kg_status kg_preempt(kg_engine *eng, const kg_pod_row *pods, const int32_t *prio
                      int64_t *pick   /* [n][8], required */,
                      uint32_t *plane /* [n][64 * W], may be NULL */, int32_t out_on_device);
 kg_status kg_preempt_merge(const int64_t *picks /* [n_lists][n][8] */, int32_t n_lists, int32_t n, int64_t *out /* [n][8] */);
+
+/* PodDisruptionBudgets in the dry run (the PDB path of preempt.go:111-267).  filterPodsWithPDBViolation walks the
+ * potential victims in importance order with one running budget per PDB; a victim at which a budget goes negative is
+ * PDB-violating.  The violating ones are reprieved first, then the others, and numViolatingVictim is upstream's first
+ * pick criterion after "a node with no victim".  The walk depends on the preemptor only through its priority and quota
+ * group and folds into one threshold per bound pod: pod s is violating for a preemptor of priority P  <=>
+ * pdb_prio(s) < P (INT32_MAX: never).  The PDB bookkeeping (namespaces, selectors, DisruptedPods) stays with the
+ * caller, where the informers are.
+ *
+ * kg_pdb_thresholds (host, no engine) computes them for one node's list in the caller's order: pod b decrements the
+ * PDBs pdb_ids[pdb_first[b] .. pdb_first[b + 1]) (indices into allowed[n_pdbs] = Status.DisruptionsAllowed; negative
+ * counts as 0) - in the reference those of its namespace with a non-empty selector that matches its labels and
+ * without its name in Status.DisruptedPods; a pod without labels has none.  Non-preemptible pods get INT32_MAX and
+ * take part in no budget.  KG_ERR_INVALID_ARG for null pointers; KG_ERR_RANGE for n outside 0..KG_BOUND_MAX_PER_NODE,
+ * offsets that do not start at 0 or do not rise, or an id outside [0, n_pdbs).
+ * Recompute a node's thresholds after a bind, a delete or a priority change on it, and after a status change of a PDB
+ * on every node that holds a pod the PDB covers.
+ *
+ * The engine keeps the thresholds in an optional plane beside the bound-pod table (allocated on first use; the table's
+ * layout does not change).  kg_bound_pdb_set loads it for every node: `first` is kg_bound_set's CSR (every node's
+ * length must equal the table's: KG_ERR_RANGE), pdb_prio in the caller's order; pdb_prio == NULL drops the plane.
+ * kg_bound_pdb_update replaces one node's values (n must equal the node's count), kg_bound_pdb_download returns them
+ * in the caller's order.  kg_bound_set and kg_snapshot_reset drop the plane; kg_bound_update resets that node's values
+ * to INT32_MAX (the list changed: follow it with kg_bound_pdb_update).  Every rank of a sharded engine loads the same
+ * plane.  KG_ERR_STATE without a table (and for _update / _download without a plane); KG_ERR_INVALID_ARG for null
+ * pointers.  h2d_bytes grows by what was uploaded.
+ *
+ * With a plane loaded kg_preempt runs the PDB form: step 5 above runs twice over the list in importance order, first
+ * over the violating potential victims, then over the others, and n_violating counts the pods of the first pass the
+ * Fit verdict made victims (the reference increments on !fits alone: a first-pass pod that the quota re-check alone
+ * makes a victim is a victim but is not counted; pinned, not repaired).  The mask, hi_prio, prio_sum and earliest_ns
+ * do not depend on the order of the victims.  To rebuild the reference's victim list from the mask: the violating
+ * victims (pdb_prio < P) in importance order, then the others in importance order.
+ *   pick word 1 = n_victims | n_violating << 32; plane cell = status | n_victims << 8 | n_potential << 16 |
+ *   n_violating << 24.  Both additions are zero without a plane.
+ * The pick order becomes: a node with no victim, the fewest n_violating, then the order above; kg_preempt_merge
+ * applies it too.  hi_prio stays the highest victim priority; the v1.24.15 evaluator reads victims.Pods[0], which with
+ * victims of both kinds is the first violating one (a stated divergence; like the rest of the pick, parity unpinned).
+ * kg_row_preempt_pdb is kg_row_preempt with bound_pdb_prio[n_bound] in the caller's order (NULL <=> none: the plain
+ * form) and stats[4] = n_violating. */
+kg_status kg_pdb_thresholds(const int32_t *priority, const int64_t *start_ns, const int32_t *quota,
+                            const uint8_t *non_preemptible, int32_t n /* one node's list, caller order */,
+                            const int32_t *pdb_first /* [n + 1] CSR */, const int32_t *pdb_ids,
+                            const int32_t *allowed /* [n_pdbs] */, int32_t n_pdbs, int32_t *pdb_prio /* [n] out */);
+kg_status kg_bound_pdb_set(kg_engine *eng, const int32_t *first /* [n_nodes + 1], as kg_bound_set */,
+                           const int32_t *pdb_prio /* NULL: drop the plane */);
+kg_status kg_bound_pdb_update(kg_engine *eng, int32_t node, const int32_t *pdb_prio, int32_t n);
+kg_status kg_bound_pdb_download(kg_engine *eng, int32_t node, int32_t *out, int32_t cap, int32_t *n);
+kg_status kg_row_preempt_pdb(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *bound,
+                             const int32_t *bound_priority, const int64_t *bound_start_ns,
+                             const int32_t *bound_pdb_prio /* NULL <=> none */, int32_t n_bound, const kg_pod_row *pod,
+                             int32_t pod_priority, const kg_quota *quotas /* NULL <=> none */, int32_t n_quotas,
+                             int64_t now_ns, int32_t *status, uint64_t victims[2],
+                             int64_t stats[5] /* n_victims, hi_prio, prio_sum, earliest_ns, n_violating */);
 
 /* Measurement: when on, every k_eval launch (kg_eval, kg_place_chunk_eval) is bracketed by a
  * pair of HIP events on the engine stream (ring of 256).  kg_eval_kernel_times writes the

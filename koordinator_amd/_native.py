@@ -74,6 +74,7 @@ PRE_CANDIDATE, PRE_ABSENT, PRE_NO_VICTIMS, PRE_UNFIT, PRE_ERROR = range(5)
 BOUND_MAX_PER_NODE = 128     # KG_BOUND_MAX_PER_NODE: bound pods of one node (bits of a victim mask)
 PREEMPT_MAX_PODS = 64        # KG_PREEMPT_MAX_PODS: preemptors of one kg_preempt call
 PREEMPT_PICK_WORDS = 8       # KG_PREEMPT_PICK_WORDS: node, n_victims, hi_prio, prio_sum, earliest_ns, mask 0, mask 1, n_candidates
+PDB_PRIO_NONE = (1 << 31) - 1   # a bound pod's PDB threshold when no preemptor makes it PDB-violating (INT32_MAX)
 START_NS_NONE = (1 << 63) - 1   # a bound pod without Status.StartTime (upstream: Now(), later than every real start)
 NODE_VALID, NODE_HAS_METRIC, NODE_HAS_UPDATE_TIME, NODE_LA_PASS_NONPROD, NODE_LA_PASS_PROD = 0x1, 0x2, 0x4, 0x8, 0x10
 NODE_NUMA_OPTIONS, NODE_NUMA_TOPO_VALID, NODE_NUMA_TOPO_INVALID = 0x40, 0x80, 0x100
@@ -261,7 +262,8 @@ EXPORTED = [
     "kg_cycle_one", "kg_batch_slot_map", "kg_pods_spill_count", "kg_elig_set", "kg_elig_update",
     "kg_pods_restricted_count", "kg_row_why", "kg_diagnose", "kg_row_unreserve", "kg_row_numa_alloc", "kg_unreserve",
     "kg_candidates", "kg_candidates_merge", "kg_bound_set", "kg_bound_update", "kg_bound_download", "kg_row_preempt",
-    "kg_preempt", "kg_preempt_merge",
+    "kg_preempt", "kg_preempt_merge", "kg_pdb_thresholds", "kg_bound_pdb_set", "kg_bound_pdb_update",
+    "kg_bound_pdb_download", "kg_row_preempt_pdb",
 ]
 
 _lib = None
@@ -327,6 +329,10 @@ def lib() -> ctypes.CDLL:
         "kg_row_preempt": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i64, vp, vp, vp]),
         "kg_preempt": (i32, [vp, vp, vp, i32, i64, ctypes.c_uint32, vp, vp, i32]),
         "kg_preempt_merge": (i32, [vp, i32, i32, vp]),
+        "kg_pdb_thresholds": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp]),
+        "kg_bound_pdb_set": (i32, [vp, vp, vp]), "kg_bound_pdb_update": (i32, [vp, i32, vp, i32]),
+        "kg_bound_pdb_download": (i32, [vp, i32, vp, i32, vp]),
+        "kg_row_preempt_pdb": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if host_only and not hasattr(L, name):

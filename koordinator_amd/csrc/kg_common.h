@@ -1868,6 +1868,7 @@ struct kg_pre_out {
     int64_t prio_sum;
     int64_t earliest_ns;
     uint64_t victims[2];         // caller positions
+    int32_t n_violating;         // numViolatingVictim (the PDB form; 0 otherwise)
 };
 // what the quota re-check reads of the preemptor's group: absent when ElasticQuota is off or the pod has no group
 struct kg_pre_quota {
@@ -1921,14 +1922,16 @@ KG_HD void kg_pre_add(kg_pre_state &st, const Src &src, int s, uint32_t res, uin
     st.pod_count += 1;
 }
 
-// Pick order of the candidates (upstream pickOneNodeForPreemption without PDBs): a node with no victim first, then the
-// lowest highest-victim priority, the lowest priority sum, the fewest victims, the latest earliest start among the
-// highest-priority victims, the lowest node index.  node < 0: no candidate (never better).
-KG_HD bool kg_pre_better(int64_t a_node, int64_t a_nv, int64_t a_hi, int64_t a_sum, int64_t a_early, int64_t b_node,
-                         int64_t b_nv, int64_t b_hi, int64_t b_sum, int64_t b_early) {
+// Pick order of the candidates (upstream pickOneNodeForPreemption): a node with no victim first, then the fewest
+// PDB-violating victims (0 on both sides without a threshold plane), the lowest highest-victim priority, the lowest
+// priority sum, the fewest victims, the latest earliest start among the highest-priority victims, the lowest node
+// index.  node < 0: no candidate (never better).
+KG_HD bool kg_pre_better(int64_t a_node, int64_t a_nvio, int64_t a_nv, int64_t a_hi, int64_t a_sum, int64_t a_early,
+                         int64_t b_node, int64_t b_nvio, int64_t b_nv, int64_t b_hi, int64_t b_sum, int64_t b_early) {
     if (a_node < 0) return false;
     if (b_node < 0) return true;
     if ((a_nv == 0) != (b_nv == 0)) return a_nv == 0;
+    if (a_nvio != b_nvio) return a_nvio < b_nvio;
     if (a_hi != b_hi) return a_hi < b_hi;
     if (a_sum != b_sum) return a_sum < b_sum;
     if (a_nv != b_nv) return a_nv < b_nv;
@@ -1940,7 +1943,11 @@ KG_HD bool kg_pre_better(int64_t a_node, int64_t a_nv, int64_t a_hi, int64_t a_s
 // compare holds with ElasticQuota off too; -1 equals -1).  `valid`: the row is KG_NODE_VALID; `rest_ok`: every part of
 // the Filter but NodeResourcesFit passes.  `st` holds the node's free amounts (of the resources kg_pre_fit_res names),
 // pod count and the group's used (of the resources of q.mask) on entry.
-template <class Src>
+// PDB: the list carries a threshold per pod (src.pdb_prio(s), kg_pdb_thresholds): a potential victim with a threshold
+// below `pp` is PDB-violating (filterPodsWithPDBViolation, preempt.go:217-267), the violating ones are reprieved first
+// and o.n_violating counts those of them the Fit verdict made victims (the reference increments on !fits alone: one
+// that the quota re-check alone makes a victim is not counted; pinned).
+template <bool PDB = false, class Src>
 KG_HD void kg_preempt_pair(const kg_consts &c, const kg_pod_dev &p, int32_t pp, int32_t g, bool valid, bool rest_ok,
                            int32_t allowed, kg_pre_state &st, const kg_pre_quota &q, const Src &src, int32_t n,
                            kg_pre_out &o) {
@@ -1948,17 +1955,25 @@ KG_HD void kg_preempt_pair(const kg_consts &c, const kg_pod_dev &p, int32_t pp, 
     o.n_potential = o.n_victims = o.hi_prio = 0;
     o.prio_sum = o.earliest_ns = 0;
     o.victims[0] = o.victims[1] = 0;
+    o.n_violating = 0;
     if (!valid) return;
     const uint32_t res = KG_WAVE_UNIFORM(kg_pre_fit_res(c, p));
     const uint32_t qres = KG_WAVE_UNIFORM(q.active ? q.mask : 0u);
     const bool q_on = KG_WAVE_UNIFORM(q.active) != 0u;
     // the potential victims, by position in importance order, all removed
     uint64_t pot0 = 0, pot1 = 0;
+    [[maybe_unused]] uint64_t vio0 = 0, vio1 = 0;
     int32_t np = 0;
     for (int s = 0; s < n; s++) {
         if (src.non_preemptible(s) || src.priority(s) >= pp || src.quota(s) != g) continue;
         if (s < 64) pot0 |= 1ull << s;
         else pot1 |= 1ull << (s - 64);
+        if constexpr (PDB) {
+            if (src.pdb_prio(s) < pp) {
+                if (s < 64) vio0 |= 1ull << s;
+                else vio1 |= 1ull << (s - 64);
+            }
+        }
         np++;
         kg_pre_remove(st, src, s, res, qres, src.numa_present(s));
     }
@@ -1973,39 +1988,86 @@ KG_HD void kg_preempt_pair(const kg_consts &c, const kg_pod_dev &p, int32_t pp, 
     }
     // reprieve in importance order
     int32_t nv = 0, hi = 0;
+    [[maybe_unused]] int32_t nvio = 0;
     int64_t sum = 0, early = 0;
     uint64_t v0 = 0, v1 = 0;
-    for (int s = 0; s < n; s++) {
-        if (!(((s < 64 ? pot0 >> s : pot1 >> (s - 64))) & 1ull)) continue;
-        const uint32_t present = src.numa_present(s);
-        kg_pre_add(st, src, s, res, qres, present);
-        bool victim = false;
-        if (!kg_pre_fits(c, p, st, allowed)) {
-            kg_pre_remove(st, src, s, res, qres, present);
-            victim = true;
-        }
-        if (q_on && !kg_pre_quota_ok(p, st, q)) {
-            if (victim) {   // the reference removes the pod a second time: NodeInfo.RemovePod errors, the node is dropped
-                o.status = KG_PRE_ERROR;
-                return;
+    if constexpr (!PDB) {
+        // TWO COPIES OF ONE BODY: the statements from `const uint32_t present` to `nv++` below and in the PDB branch
+        // are the same text but for the nvio line; a change to one is a change to both.  (Kept apart because k_preempt
+        // sits at the VGPR ceiling and a shared body moved the plain kernels' register allocation; the PDB form under
+        // all-INT32_MAX thresholds is tested equal to this one.)
+        for (int s = 0; s < n; s++) {
+            if (!(((s < 64 ? pot0 >> s : pot1 >> (s - 64))) & 1ull)) continue;
+            const uint32_t present = src.numa_present(s);
+            kg_pre_add(st, src, s, res, qres, present);
+            bool victim = false;
+            if (!kg_pre_fits(c, p, st, allowed)) {
+                kg_pre_remove(st, src, s, res, qres, present);
+                victim = true;
             }
-            kg_pre_remove(st, src, s, res, qres, present);
-            victim = true;
+            if (q_on && !kg_pre_quota_ok(p, st, q)) {
+                if (victim) {   // the reference removes the pod a second time: NodeInfo.RemovePod errors, the node is dropped
+                    o.status = KG_PRE_ERROR;
+                    return;
+                }
+                kg_pre_remove(st, src, s, res, qres, present);
+                victim = true;
+            }
+            if (!victim) continue;
+            const int32_t pr = src.priority(s);
+            const int64_t t = src.start_ns(s);
+            const int pos = src.position(s);
+            if (pos < 64) v0 |= 1ull << pos;
+            else v1 |= 1ull << (pos - 64);
+            if (nv == 0 || pr > hi) {
+                hi = pr;
+                early = t;
+            } else if (pr == hi && t < early) {
+                early = t;
+            }
+            sum += (int64_t)pr + 2147483648LL;
+            nv++;
         }
-        if (!victim) continue;
-        const int32_t pr = src.priority(s);
-        const int64_t t = src.start_ns(s);
-        const int pos = src.position(s);
-        if (pos < 64) v0 |= 1ull << pos;
-        else v1 |= 1ull << (pos - 64);
-        if (nv == 0 || pr > hi) {
-            hi = pr;
-            early = t;
-        } else if (pr == hi && t < early) {
-            early = t;
+    } else {
+        // the same body (the second copy: see above) twice over the list: first the violating potential victims, then
+        // the others
+#pragma unroll 1
+        for (int pass = 0; pass < 2; pass++) {
+            const uint64_t w0 = pass == 0 ? (pot0 & vio0) : (pot0 & ~vio0), w1 = pass == 0 ? (pot1 & vio1) : (pot1 & ~vio1);
+            for (int s = 0; s < n; s++) {
+                if (!(((s < 64 ? w0 >> s : w1 >> (s - 64))) & 1ull)) continue;
+                const uint32_t present = src.numa_present(s);
+                kg_pre_add(st, src, s, res, qres, present);
+                bool victim = false;
+                if (!kg_pre_fits(c, p, st, allowed)) {
+                    kg_pre_remove(st, src, s, res, qres, present);
+                    victim = true;
+                    nvio += pass == 0 ? 1 : 0;   // (on !fits alone: the quota re-check below does not count)
+                }
+                if (q_on && !kg_pre_quota_ok(p, st, q)) {
+                    if (victim) {   // the reference removes the pod a second time: NodeInfo.RemovePod errors, the node is dropped
+                        o.status = KG_PRE_ERROR;
+                        return;
+                    }
+                    kg_pre_remove(st, src, s, res, qres, present);
+                    victim = true;
+                }
+                if (!victim) continue;
+                const int32_t pr = src.priority(s);
+                const int64_t t = src.start_ns(s);
+                const int pos = src.position(s);
+                if (pos < 64) v0 |= 1ull << pos;
+                else v1 |= 1ull << (pos - 64);
+                if (nv == 0 || pr > hi) {
+                    hi = pr;
+                    early = t;
+                } else if (pr == hi && t < early) {
+                    early = t;
+                }
+                sum += (int64_t)pr + 2147483648LL;
+                nv++;
+            }
         }
-        sum += (int64_t)pr + 2147483648LL;
-        nv++;
     }
     o.status = KG_PRE_CANDIDATE;
     o.n_victims = nv;
@@ -2014,4 +2076,5 @@ KG_HD void kg_preempt_pair(const kg_consts &c, const kg_pod_dev &p, int32_t pp, 
     o.earliest_ns = early;
     o.victims[0] = v0;
     o.victims[1] = v1;
+    if constexpr (PDB) o.n_violating = nvio;
 }

@@ -92,6 +92,8 @@
 //                                     records, quota group (read)
 //   138-139 k_preempt_pick            per-(pod, tile) records (read), pick
 //   140-141 k_bound_update            staged record (read), bound table slot and node
+//   142     k_preempt (PDB forms)     threshold plane slot and node (read)
+//   143-144 k_bound_pdb_fill          staged thresholds (read), threshold plane slot and node
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -3762,6 +3764,7 @@ struct BoundSrc {
     const int64_t *__restrict__ tab;
     int64_t cap, node;
     int32_t max_per_node;
+    const int32_t *__restrict__ pdb;
     __device__ __forceinline__ int64_t f(int s, int fld) const {
         return KG_IN2(134, s, max_per_node, node, cap) ? tab[((int64_t)s * KG_BOUND_FIELDS + fld) * cap + node] : 0;
     }
@@ -3773,6 +3776,10 @@ struct BoundSrc {
     __device__ __forceinline__ int32_t priority(int s) const { return (int32_t)(uint32_t)(uint64_t)f(s, KG_BF_META); }
     __device__ __forceinline__ int64_t start_ns(int s) const { return f(s, KG_BF_START); }
     __device__ __forceinline__ int position(int s) const { return (int)(((uint64_t)f(s, KG_BF_META) >> 32) & 0xFFull); }
+    // the PDB threshold of slot s: one coalesced 32-bit load over the wave's nodes
+    __device__ __forceinline__ int32_t pdb_prio(int s) const {
+        return KG_IN2(142, s, max_per_node, node, cap) ? pdb[(int64_t)s * cap + node] : INT32_MAX;
+    }
 };
 
 struct PreArgs {
@@ -3793,10 +3800,20 @@ struct PrePod {
     kg_pre_quota q;
     int32_t prio, group;
 };
-// a pick record in flight: the order of kg_pre_better
+// a pick record in flight: the order of kg_pre_better.  nv: n_victims | n_violating << 32 (word 1 of a record; the
+// high half is 0 without a threshold plane, and only the PDB forms read it)
 struct PreRec {
     int64_t node, nv, hi, sum, early;
 };
+template <bool PDB>
+__device__ __forceinline__ bool pre_rec_better(const PreRec &a, const PreRec &b) {
+    if constexpr (PDB)
+        return kg_pre_better(a.node, a.nv >> 32, a.nv & 0xFFFFFFFFll, a.hi, a.sum, a.early, b.node, b.nv >> 32,
+                             b.nv & 0xFFFFFFFFll, b.hi, b.sum, b.early);
+    else
+        return kg_pre_better(a.node, 0, a.nv, a.hi, a.sum, a.early, b.node, 0, b.nv, b.hi, b.sum, b.early);
+}
+template <bool PDB>
 __device__ __forceinline__ void pre_wave_best(PreRec &r) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
@@ -3806,7 +3823,7 @@ __device__ __forceinline__ void pre_wave_best(PreRec &r) {
         o.hi = __shfl_xor(r.hi, off, 64);
         o.sum = __shfl_xor(r.sum, off, 64);
         o.early = __shfl_xor(r.early, off, 64);
-        if (kg_pre_better(o.node, o.nv, o.hi, o.sum, o.early, r.node, r.nv, r.hi, r.sum, r.early)) r = o;
+        if (pre_rec_better<PDB>(o, r)) r = o;
     }
 }
 #define KG_PRE_WAVES (KG_BLOCK / 64)
@@ -3822,11 +3839,15 @@ __device__ __forceinline__ void pre_wave_best(PreRec &r) {
 // padded row.  Pick: the wave's best candidate by shuffles, the winning lane writes its record and mask to LDS; a wave
 // per pod then reduces the workgroup's 16 records and stores the (pod, tile) record and candidate count into `slab`
 // [n][shard_tiles][8] with plain stores, every word of it: no atomics.
-template <bool PLANE>
+// PDB (launched only with a threshold plane loaded): the pair routine's PDB form over `pdb` ([max_per_node][cap]
+// thresholds, kg_bound_pdb_set; the plain forms never read the argument); the cell gains n_violating << 24 and word 1
+// of a record n_violating << 32.  The plain forms compile to what they were without it.
+template <bool PLANE, bool PDB>
 __global__ __launch_bounds__(KG_BLOCK) void k_preempt(kg_consts c, kg_planes pl, PreArgs a,
                                                       const kg_pod_dev *__restrict__ pods,
                                                       const int32_t *__restrict__ prio, const int32_t *__restrict__ group,
-                                                      uint32_t *__restrict__ plane, int64_t *__restrict__ slab) {
+                                                      uint32_t *__restrict__ plane, int64_t *__restrict__ slab,
+                                                      const int32_t *__restrict__ pdb) {
     __shared__ __attribute__((aligned(16))) kg_pod_dev lp[KG_SPILL_CHUNK];
     __shared__ PrePod lq[KG_SPILL_CHUNK];
     __shared__ int64_t lrec[KG_SPILL_CHUNK][KG_PRE_SLOTS][8];
@@ -3873,7 +3894,7 @@ __global__ __launch_bounds__(KG_BLOCK) void k_preempt(kg_consts c, kg_planes pl,
             const int32_t cnt0 = in ? pl.rows[node].pod_count : 0, allowed = in ? pl.rows[node].allowed_pods : 0;
             const int32_t nb = in ? a.bt.count[node] : 0, npre = in ? a.bt.n_pre[node] : 0;
             const int32_t minp = in ? a.bt.min_prio[node] : INT32_MAX;
-            const BoundSrc src{a.bt.tab, a.bt.cap, node, a.bt.max_per_node};
+            const BoundSrc src{a.bt.tab, a.bt.cap, node, a.bt.max_per_node, PDB ? pdb : nullptr};
             const int64_t col = wave_base + 64 * h - a.col_begin;   // wave-uniform
             [[maybe_unused]] const bool seg = col < a.stride;
             for (int j = 0; j < nq; j++) {
@@ -3886,6 +3907,7 @@ __global__ __launch_bounds__(KG_BLOCK) void k_preempt(kg_consts c, kg_planes pl,
                     o.n_potential = o.n_victims = o.hi_prio = 0;
                     o.prio_sum = o.earliest_ns = 0;
                     o.victims[0] = o.victims[1] = 0;
+                    o.n_violating = 0;
                 } else {
                     // the free amounts the pod's Fit compares read (a coalesced load per resource, wave-uniform choice)
                     // and the group's used of the resources the re-check reads
@@ -3898,17 +3920,19 @@ __global__ __launch_bounds__(KG_BLOCK) void k_preempt(kg_consts c, kg_planes pl,
                     }
                     st.pod_count = cnt0;
                     const bool rest_ok = kg_elig_ok(pl, p, node) && kg_why_la(c, df, expired, p) == 0u;
-                    kg_preempt_pair(c, p, pq.prio, pq.group, valid, rest_ok, allowed, st, pq.q, src, valid ? nb : 0, o);
+                    kg_preempt_pair<PDB>(c, p, pq.prio, pq.group, valid, rest_ok, allowed, st, pq.q, src, valid ? nb : 0, o);
                 }
                 const bool cand = in && o.status == KG_PRE_CANDIDATE;
                 if constexpr (PLANE) {
                     const int pi = q0 + j;
                     if (seg && KG_IN2(135, pi, a.n_pods, col + lane, a.stride))
                         plane[(int64_t)pi * a.stride + col + lane] =
-                            (uint32_t)o.status | ((uint32_t)(cand ? o.n_victims : 0) << 8) | ((uint32_t)o.n_potential << 16);
+                            (uint32_t)o.status | ((uint32_t)(cand ? o.n_victims : 0) << 8) | ((uint32_t)o.n_potential << 16) |
+                            (PDB ? (uint32_t)(cand ? o.n_violating : 0) << 24 : 0u);
                 }
                 PreRec best{cand ? node : -1, o.n_victims, o.hi_prio, o.prio_sum, o.earliest_ns};
-                pre_wave_best(best);
+                if constexpr (PDB) best.nv |= (int64_t)o.n_violating << 32;
+                pre_wave_best<PDB>(best);
                 const int slot = wave * 2 + h;
                 if (best.node < 0 ? lane == 0 : (cand && node == best.node)) {
                     int64_t *d = lrec[j][slot];
@@ -3940,7 +3964,7 @@ __global__ __launch_bounds__(KG_BLOCK) void k_preempt(kg_consts c, kg_planes pl,
             uint32_t nc = has ? lcand[j][lane] : 0u;
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) nc += __shfl_xor(nc, off, 64);
-            pre_wave_best(best);
+            pre_wave_best<PDB>(best);
             if (best.node < 0 ? lane == 0 : (has && mine == best.node)) {
                 if (KG_IN2(136, pi, a.n_pods, tile_rel, a.shard_tiles)) {
                     int64_t *d = slab + ((int64_t)pi * a.shard_tiles + tile_rel) * 8;
@@ -3960,7 +3984,7 @@ __global__ __launch_bounds__(KG_BLOCK) void k_preempt(kg_consts c, kg_planes pl,
 }
 
 // The pick of each pod over the tiles' records: a wave per pod, lane t takes tiles t, t + 64, ..., the wave's best by
-// the same shuffles, the candidate counts summed; every word of pick[p] is written (node -1: the others 0).
+// the same shuffles (word 1 split into n_victims and n_violating, which is 0 without a plane), the candidate counts summed; every word of pick[p] is written (node -1: the others 0).
 __global__ __launch_bounds__(64) void k_preempt_pick(const int64_t *__restrict__ slab, int32_t n_pods, int32_t tiles,
                                                      int64_t *__restrict__ pick) {
     const int p = blockIdx.x, lane = threadIdx.x;
@@ -3971,8 +3995,9 @@ __global__ __launch_bounds__(64) void k_preempt_pick(const int64_t *__restrict__
         if (!KG_IN2(138, p, n_pods, t, tiles)) continue;
         const int64_t *d = slab + ((int64_t)p * tiles + t) * 8;
         nc += d[7];
-        if (kg_pre_better(d[0], d[1], d[2], d[3], d[4], best.node, best.nv, best.hi, best.sum, best.early)) {
-            best = PreRec{d[0], d[1], d[2], d[3], d[4]};
+        const PreRec r{d[0], d[1], d[2], d[3], d[4]};
+        if (pre_rec_better<true>(r, best)) {
+            best = r;
             m0 = d[5];
             m1 = d[6];
         }
@@ -3980,7 +4005,7 @@ __global__ __launch_bounds__(64) void k_preempt_pick(const int64_t *__restrict__
     const int64_t mine = best.node;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) nc += __shfl_xor(nc, off, 64);
-    pre_wave_best(best);
+    pre_wave_best<true>(best);
     if ((best.node < 0 ? lane == 0 : mine == best.node) && KG_IN(139, p, n_pods)) {
         int64_t *d = pick + (int64_t)p * KG_PREEMPT_PICK_WORDS;
         const bool none = best.node < 0;
@@ -4010,6 +4035,16 @@ __global__ void k_bound_update(int64_t *__restrict__ tab, int32_t *__restrict__ 
     const int s = k / KG_BOUND_FIELDS, f = k - s * KG_BOUND_FIELDS;
     if (KG_IN(140, k, (int64_t)n * KG_BOUND_FIELDS) && KG_IN2(141, s, max_per_node, node, cap))
         tab[((int64_t)s * KG_BOUND_FIELDS + f) * cap + node] = staged[k];
+}
+
+// kg_bound_pdb_update / kg_bound_update: one node's column of the threshold plane, slot s < n from `staged` (importance
+// order; nullptr: none) and INT32_MAX in every other slot
+__global__ void k_bound_pdb_fill(int32_t *__restrict__ pdb, int64_t cap, int32_t max_per_node, int64_t node,
+                                 const int32_t *__restrict__ staged, int32_t n) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= max_per_node) return;
+    const int32_t v = (staged && s < n && KG_IN(143, s, n)) ? staged[s] : INT32_MAX;
+    if (KG_IN2(144, s, max_per_node, node, cap)) pdb[(int64_t)s * cap + node] = v;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -4382,6 +4417,12 @@ struct kg_engine {
     int64_t *bound_tab = nullptr;
     int32_t *bound_count = nullptr, *bound_npre = nullptr, *bound_minprio = nullptr;
     int32_t bound_max = 0;
+    // host mirror of the lists' shape: the length of every node's list and, per (node, slot), the caller position of the
+    // pod in that slot (what maps kg_bound_pdb_*'s caller-order values to slots without a read-back)
+    std::vector<int32_t> bound_len;
+    std::vector<uint8_t> bound_pos;   // [n_nodes][bound_max]
+    // the PDB threshold plane (kg_bound_pdb_set): pdb[slot * cap + node], allocated on first use, nullptr: none loaded
+    int32_t *bound_pdb = nullptr;
     // kg_preempt: the call's pod rows, priorities, groups, staged outputs and per-(pod, tile) records on the device (one
     // buffer, grown on demand) and the pinned host block its inputs pass through
     void *pre_mem = nullptr;
@@ -5424,6 +5465,7 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->cand_mem) (void)hipFree(e->cand_mem);
     if (e->cand_host) (void)hipHostFree(e->cand_host);
     if (e->bound_mem) (void)hipFree(e->bound_mem);
+    if (e->bound_pdb) (void)hipFree(e->bound_pdb);
     if (e->pre_mem) (void)hipFree(e->pre_mem);
     if (e->pre_host) (void)hipHostFree(e->pre_host);
     if (e->unr_mem) (void)hipFree(e->unr_mem);
@@ -5543,6 +5585,10 @@ kg_status kg_snapshot_reset(kg_engine *e, int32_t n_nodes) {
     e->bound_tab = nullptr;
     e->bound_count = e->bound_npre = e->bound_minprio = nullptr;
     e->bound_max = 0;
+    if (e->bound_pdb) HIP_TRY(e, hipFree(e->bound_pdb));  // and its PDB threshold plane
+    e->bound_pdb = nullptr;
+    e->bound_len.clear();
+    e->bound_pos.clear();
     e->pl.cap = cap;
     e->n_nodes = n_nodes;
     e->node_bind_facts.assign((size_t)n_nodes, 0);
@@ -7548,13 +7594,17 @@ kg_status kg_bound_set(kg_engine *e, const int32_t *first, const kg_pod_row *row
     const size_t tab_n = (size_t)max_per_node * KG_BOUND_FIELDS * (size_t)cap;
     std::vector<int64_t> tab(tab_n, 0);
     std::vector<int32_t> sum(3 * (size_t)cap, 0);
+    std::vector<int32_t> len((size_t)N, 0);
+    std::vector<uint8_t> posn((size_t)N * (size_t)max_per_node, 0);
     int32_t order[KG_BOUND_MAX_PER_NODE];
     int64_t rec[KG_BOUND_FIELDS];
     for (int64_t j = 0; j < cap; j++) sum[2 * (size_t)cap + (size_t)j] = INT32_MAX;
     for (int64_t j = 0; j < N; j++) {
         const int32_t b = first[j], n = first[j + 1] - b;
         kg_bound_order(priority + b, start_ns + b, n, order);
+        len[(size_t)j] = n;
         for (int32_t s = 0; s < n; s++) {
+            posn[(size_t)j * (size_t)max_per_node + (size_t)s] = (uint8_t)order[s];
             bound_pack(rows[b + order[s]], priority[b + order[s]], start_ns[b + order[s]], order[s], rec);
             for (int f = 0; f < KG_BOUND_FIELDS; f++) tab[((size_t)s * KG_BOUND_FIELDS + (size_t)f) * (size_t)cap + (size_t)j] = rec[f];
         }
@@ -7571,6 +7621,10 @@ kg_status kg_bound_set(kg_engine *e, const int32_t *first, const kg_pod_row *row
     e->bound_tab = nullptr;
     e->bound_count = e->bound_npre = e->bound_minprio = nullptr;
     e->bound_max = 0;
+    if (e->bound_pdb) HIP_TRY(e, hipFree(e->bound_pdb));   // the thresholds belonged to the lists replaced
+    e->bound_pdb = nullptr;
+    e->bound_len.clear();
+    e->bound_pos.clear();
     const size_t tab_b = (tab_n * 8 + 255) / 256 * 256, sum_b = sum.size() * 4;
     HIP_TRY(e, hipMalloc(&e->bound_mem, tab_b + sum_b));
     HIP_TRY(e, h2d(e, e->bound_mem, tab.data(), tab_n * 8, e->stream));
@@ -7581,6 +7635,8 @@ kg_status kg_bound_set(kg_engine *e, const int32_t *first, const kg_pod_row *row
     e->bound_npre = e->bound_count + cap;
     e->bound_minprio = e->bound_npre + cap;
     e->bound_max = max_per_node;
+    e->bound_len.swap(len);
+    e->bound_pos.swap(posn);
     return KG_OK;
 }
 
@@ -7613,6 +7669,15 @@ kg_status kg_bound_update(kg_engine *e, int32_t node, const kg_pod_row *rows, co
                        e->bound_count, e->bound_npre, e->bound_minprio, e->pl.cap, e->bound_max, (int64_t)node,
                        (const int64_t *)e->scratch, n, pre, minp);
     HIP_TRY(e, hipGetLastError());
+    // the new list is in the stream: the host mirror follows it here, ahead of every later early return, so the
+    // threshold calls never map through a list the device no longer holds
+    e->bound_len[(size_t)node] = n;
+    for (int32_t s = 0; s < n; s++) e->bound_pos[(size_t)node * (size_t)e->bound_max + (size_t)s] = (uint8_t)order[s];
+    if (e->bound_pdb) {   // the list changed: its thresholds no longer apply (kg_bound_pdb_update follows)
+        hipLaunchKernelGGL(k_bound_pdb_fill, dim3(1), dim3(KG_BOUND_MAX_PER_NODE), 0, e->stream, e->bound_pdb, e->pl.cap,
+                           e->bound_max, (int64_t)node, (const int32_t *)nullptr, 0);
+        HIP_TRY(e, hipGetLastError());
+    }
     HIP_TRY(e, hipStreamSynchronize(e->stream));   // staging buffer reuse
     return bounds_verdict(e);
 }
@@ -7648,6 +7713,90 @@ kg_status kg_bound_download(kg_engine *e, int32_t node, kg_pod_row *rows, int32_
         priority[pos] = prio;
         start_ns[pos] = t;
     }
+    return KG_OK;
+}
+
+// ---- the PDB threshold plane (kg_bound_pdb_set / _update / _download) --------------------------------------------
+// One int32 per bound pod (kg_pdb_thresholds), slot-major beside the table: pdb[slot * cap + node].  The caller hands
+// the values in its own order; the host mirror of the lists maps them to slots.
+kg_status kg_bound_pdb_set(kg_engine *e, const int32_t *first, const int32_t *pdb_prio) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised (kg_snapshot_reset)");
+    if (!e->bound_mem) return set_err(e, KG_ERR_STATE, "no bound-pod table (kg_bound_set)");
+    if (!pdb_prio) {   // drop the plane
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (e->bound_pdb) HIP_TRY(e, hipFree(e->bound_pdb));
+        e->bound_pdb = nullptr;
+        return KG_OK;
+    }
+    if (!first) return set_err(e, KG_ERR_INVALID_ARG, "null offsets");
+    const int64_t N = e->n_nodes, cap = e->pl.cap;
+    if (first[0] != 0) return set_err(e, KG_ERR_RANGE, "offsets do not start at 0");
+    for (int64_t j = 0; j < N; j++)
+        if (first[j + 1] - first[j] != e->bound_len[(size_t)j])
+            return set_err(e, KG_ERR_RANGE, "node %lld: %d thresholds, the table holds %d bound pods", (long long)j,
+                           first[j + 1] - first[j], e->bound_len[(size_t)j]);
+    const size_t n_cells = (size_t)e->bound_max * (size_t)cap;
+    std::vector<int32_t> img(n_cells, INT32_MAX);
+    for (int64_t j = 0; j < N; j++) {
+        const int32_t b = first[j], n = e->bound_len[(size_t)j];
+        const uint8_t *pos = e->bound_pos.data() + (size_t)j * (size_t)e->bound_max;
+        for (int32_t s = 0; s < n; s++) img[(size_t)s * (size_t)cap + (size_t)j] = pdb_prio[b + pos[s]];
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // evaluations in flight finish first
+    if (e->eval_stream) HIP_TRY(e, hipStreamSynchronize(e->eval_stream));
+    if (!e->bound_pdb) HIP_TRY(e, hipMalloc((void **)&e->bound_pdb, n_cells * 4));
+    HIP_TRY(e, h2d(e, e->bound_pdb, img.data(), n_cells * 4, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the host image goes out of scope)
+    return KG_OK;
+}
+
+kg_status kg_bound_pdb_update(kg_engine *e, int32_t node, const int32_t *pdb_prio, int32_t n) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised (kg_snapshot_reset)");
+    if (!e->bound_mem) return set_err(e, KG_ERR_STATE, "no bound-pod table (kg_bound_set)");
+    if (!e->bound_pdb) return set_err(e, KG_ERR_STATE, "no PDB threshold plane (kg_bound_pdb_set)");
+    if (node < 0 || node >= e->n_nodes) return set_err(e, KG_ERR_RANGE, "node %d outside the snapshot", node);
+    if (n != e->bound_len[(size_t)node])
+        return set_err(e, KG_ERR_RANGE, "node %d: %d thresholds, the table holds %d bound pods", node, n, e->bound_len[(size_t)node]);
+    if (n > 0 && !pdb_prio) return set_err(e, KG_ERR_INVALID_ARG, "null thresholds");
+    int32_t staged[KG_BOUND_MAX_PER_NODE];
+    const uint8_t *pos = e->bound_pos.data() + (size_t)node * (size_t)e->bound_max;
+    for (int32_t s = 0; s < n; s++) staged[s] = pdb_prio[pos[s]];
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // evaluations in flight finish first
+    if (e->eval_stream) HIP_TRY(e, hipStreamSynchronize(e->eval_stream));
+    st = ensure_scratch(e, sizeof(staged) + 256);
+    if (st) return st;
+    if (n > 0) HIP_TRY(e, h2d(e, e->scratch, staged, (size_t)n * 4, e->stream));
+    hipLaunchKernelGGL(k_bound_pdb_fill, dim3(1), dim3(KG_BOUND_MAX_PER_NODE), 0, e->stream, e->bound_pdb, e->pl.cap,
+                       e->bound_max, (int64_t)node, (const int32_t *)e->scratch, n);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // staging buffer reuse
+    return bounds_verdict(e);
+}
+
+kg_status kg_bound_pdb_download(kg_engine *e, int32_t node, int32_t *out, int32_t cap, int32_t *n) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    if (!n) return set_err(e, KG_ERR_INVALID_ARG, "null count");
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised (kg_snapshot_reset)");
+    if (!e->bound_mem) return set_err(e, KG_ERR_STATE, "no bound-pod table (kg_bound_set)");
+    if (!e->bound_pdb) return set_err(e, KG_ERR_STATE, "no PDB threshold plane (kg_bound_pdb_set)");
+    if (node < 0 || node >= e->n_nodes) return set_err(e, KG_ERR_RANGE, "node %d outside the snapshot", node);
+    if (cap < 0 || cap > e->bound_max) return set_err(e, KG_ERR_RANGE, "capacity %d, the table keeps %d per node", cap, e->bound_max);
+    if (cap > 0 && !out) return set_err(e, KG_ERR_INVALID_ARG, "null thresholds");
+    const int32_t have = e->bound_len[(size_t)node];
+    *n = have;
+    if (have > cap) return set_err(e, KG_ERR_RANGE, "node %d holds %d bound pods, capacity %d", node, have, cap);
+    if (have == 0) return KG_OK;
+    int32_t col[KG_BOUND_MAX_PER_NODE];   // the node's column: one 4-byte element per slot, a plane row apart
+    HIP_TRY(e, hipMemcpy2DAsync(col, 4, e->bound_pdb + node, (size_t)e->pl.cap * 4, 4, (size_t)have, hipMemcpyDeviceToHost,
+                                e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    const uint8_t *pos = e->bound_pos.data() + (size_t)node * (size_t)e->bound_max;
+    for (int32_t s = 0; s < have; s++) out[pos[s]] = col[s];
     return KG_OK;
 }
 
@@ -7759,8 +7908,11 @@ kg_status kg_preempt(kg_engine *e, const kg_pod_row *pods, const int32_t *priori
     a.n_quota = e->n_quota;
     a.quota = (plug & KG_PLUGIN_ELASTICQUOTA) ? (const kg_quota *)e->quota : (const kg_quota *)nullptr;
     a.bt = BoundTab{e->bound_tab, e->bound_count, e->bound_npre, e->bound_minprio, e->pl.cap, e->bound_max};
-    hipLaunchKernelGGL(plane_d ? k_preempt<true> : k_preempt<false>, dim3((unsigned)blocks), dim3(KG_BLOCK), 0, e->stream,
-                       e->consts, e->pl, a, pods_d, prio_d, grp_d, plane_d, slab);
+    // the PDB forms only with a threshold plane loaded
+    auto kern = e->bound_pdb ? (plane_d ? k_preempt<true, true> : k_preempt<false, true>)
+                             : (plane_d ? k_preempt<true, false> : k_preempt<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(KG_BLOCK), 0, e->stream,
+                       e->consts, e->pl, a, pods_d, prio_d, grp_d, plane_d, slab, (const int32_t *)e->bound_pdb);
     HIP_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(k_preempt_pick, dim3((unsigned)n), dim3(64), 0, e->stream, (const int64_t *)slab, n, (int32_t)shard_tiles,
                        pick_d);

@@ -891,6 +891,7 @@ struct RowBoundSrc {
     const int32_t *prio;
     const int64_t *start;
     const int32_t *order;
+    const int32_t *pdb;   // thresholds in the caller's order (the PDB form only)
     int64_t req(int s, int r) const { return rows[order[s]].request[r]; }
     int64_t numa_req(int s, int r) const { return rows[order[s]].numa_request[r]; }
     uint32_t numa_present(int s) const { return rows[order[s]].numa_request_present; }
@@ -899,13 +900,15 @@ struct RowBoundSrc {
     int32_t priority(int s) const { return prio[order[s]]; }
     int64_t start_ns(int s) const { return start[order[s]]; }
     int position(int s) const { return order[s]; }
+    int32_t pdb_prio(int s) const { return pdb[order[s]]; }
 };
-}  // namespace
 
-kg_status kg_row_preempt(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *bound, const int32_t *bound_priority,
-                         const int64_t *bound_start_ns, int32_t n_bound, const kg_pod_row *pod, int32_t pod_priority,
-                         const kg_quota *quotas, int32_t n_quotas, int64_t now_ns, int32_t *status, uint64_t victims[2],
-                         int64_t stats[4]) {
+// kg_row_preempt and kg_row_preempt_pdb: `pdb` NULL runs the plain form of the pair routine; stats[4] is written only
+// when `n_stats` is 5
+kg_status row_preempt(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *bound, const int32_t *bound_priority,
+                      const int64_t *bound_start_ns, const int32_t *pdb, int32_t n_bound, const kg_pod_row *pod,
+                      int32_t pod_priority, const kg_quota *quotas, int32_t n_quotas, int64_t now_ns, int32_t *status,
+                      uint64_t victims[2], int64_t *stats, int n_stats) {
     if (!cfg || !node || !pod || !status || !victims || !stats) return KG_ERR_INVALID_ARG;
     if (n_bound < 0 || n_bound > KG_BOUND_MAX_PER_NODE) return KG_ERR_RANGE;
     if (n_bound > 0 && (!bound || !bound_priority || !bound_start_ns)) return KG_ERR_INVALID_ARG;
@@ -941,9 +944,10 @@ kg_status kg_row_preempt(const kg_config *cfg, const kg_node_row *node, const kg
     }
     int32_t order[KG_BOUND_MAX_PER_NODE];
     kg_bound_order(bound_priority, bound_start_ns, n_bound, order);
-    const RowBoundSrc src{bound, bound_priority, bound_start_ns, order};
+    const RowBoundSrc src{bound, bound_priority, bound_start_ns, order, pdb};
     kg_pre_out o;
-    kg_preempt_pair(k, pd, pod_priority, pod->quota, valid, rest_ok, row.allowed_pods, st, q, src, n_bound, o);
+    if (pdb) kg_preempt_pair<true>(k, pd, pod_priority, pod->quota, valid, rest_ok, row.allowed_pods, st, q, src, n_bound, o);
+    else kg_preempt_pair<false>(k, pd, pod_priority, pod->quota, valid, rest_ok, row.allowed_pods, st, q, src, n_bound, o);
     *status = o.status;
     const bool cand = o.status == KG_PRE_CANDIDATE;
     victims[0] = cand ? o.victims[0] : 0;
@@ -952,11 +956,72 @@ kg_status kg_row_preempt(const kg_config *cfg, const kg_node_row *node, const kg
     stats[1] = cand ? o.hi_prio : 0;
     stats[2] = cand ? o.prio_sum : 0;
     stats[3] = cand ? o.earliest_ns : 0;
+    if (n_stats > 4) stats[4] = cand ? o.n_violating : 0;
+    return KG_OK;
+}
+}  // namespace
+
+kg_status kg_row_preempt(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *bound, const int32_t *bound_priority,
+                         const int64_t *bound_start_ns, int32_t n_bound, const kg_pod_row *pod, int32_t pod_priority,
+                         const kg_quota *quotas, int32_t n_quotas, int64_t now_ns, int32_t *status, uint64_t victims[2],
+                         int64_t stats[4]) {
+    return row_preempt(cfg, node, bound, bound_priority, bound_start_ns, nullptr, n_bound, pod, pod_priority, quotas, n_quotas,
+                       now_ns, status, victims, stats, 4);
+}
+
+kg_status kg_row_preempt_pdb(const kg_config *cfg, const kg_node_row *node, const kg_pod_row *bound,
+                             const int32_t *bound_priority, const int64_t *bound_start_ns, const int32_t *bound_pdb_prio,
+                             int32_t n_bound, const kg_pod_row *pod, int32_t pod_priority, const kg_quota *quotas,
+                             int32_t n_quotas, int64_t now_ns, int32_t *status, uint64_t victims[2], int64_t stats[5]) {
+    return row_preempt(cfg, node, bound, bound_priority, bound_start_ns, bound_pdb_prio, n_bound, pod, pod_priority, quotas,
+                       n_quotas, now_ns, status, victims, stats, 5);
+}
+
+// kg_pdb_thresholds (koord_gpu.h): filterPodsWithPDBViolation's running budgets (preempt.go:217-267) folded into one
+// priority per pod.  Per (group, PDB) the chain of covered preemptible pods in importance order; the budget of PDB i
+// goes negative at the chain's k-th member exactly when member k - max(0, allowed_i) exists and is a potential victim,
+// i.e. has a priority below the preemptor's: that member's priority is the threshold, the lowest over the pod's PDBs.
+kg_status kg_pdb_thresholds(const int32_t *priority, const int64_t *start_ns, const int32_t *quota,
+                            const uint8_t *non_preemptible, int32_t n, const int32_t *pdb_first, const int32_t *pdb_ids,
+                            const int32_t *allowed, int32_t n_pdbs, int32_t *pdb_prio) {
+    if (n < 0 || n > KG_BOUND_MAX_PER_NODE || n_pdbs < 0) return KG_ERR_RANGE;
+    if (!pdb_first) return KG_ERR_INVALID_ARG;
+    if (n > 0 && (!priority || !start_ns || !quota || !non_preemptible || !pdb_prio)) return KG_ERR_INVALID_ARG;
+    if (n_pdbs > 0 && !allowed) return KG_ERR_INVALID_ARG;
+    if (pdb_first[0] != 0) return KG_ERR_RANGE;
+    for (int32_t i = 0; i < n; i++)
+        if (pdb_first[i + 1] < pdb_first[i]) return KG_ERR_RANGE;
+    const int32_t total = pdb_first[n];
+    if (total > 0 && !pdb_ids) return KG_ERR_INVALID_ARG;
+    for (int32_t k = 0; k < total; k++)
+        if (pdb_ids[k] < 0 || pdb_ids[k] >= n_pdbs) return KG_ERR_RANGE;
+    int32_t order[KG_BOUND_MAX_PER_NODE];
+    kg_bound_order(priority, start_ns, n, order);
+    for (int32_t i = 0; i < n; i++) pdb_prio[i] = INT32_MAX;
+    int32_t chain[KG_BOUND_MAX_PER_NODE];   // the priorities of the chain of (group of s, PDB i) up to s
+    for (int32_t s = 0; s < n; s++) {
+        const int32_t me = order[s];
+        if (non_preemptible[me]) continue;
+        for (int32_t k = pdb_first[me]; k < pdb_first[me + 1]; k++) {
+            const int32_t pdb = pdb_ids[k];
+            int32_t len = 0;
+            for (int32_t t = 0; t <= s; t++) {
+                const int32_t o = order[t];
+                if (non_preemptible[o] || quota[o] != quota[me]) continue;
+                bool covered = false;
+                for (int32_t m = pdb_first[o]; m < pdb_first[o + 1] && !covered; m++) covered = pdb_ids[m] == pdb;
+                if (covered) chain[len++] = priority[o];
+            }
+            const int64_t a = allowed[pdb] > 0 ? allowed[pdb] : 0;
+            const int64_t at = (int64_t)len - a;   // 1-based position of the deciding member (s itself is member `len`)
+            if (at >= 1 && chain[at - 1] < pdb_prio[me]) pdb_prio[me] = chain[at - 1];
+        }
+    }
     return KG_OK;
 }
 
 // kg_preempt_merge (koord_gpu.h): the picks of several shards or ranks for the same pods, the better one by
-// kg_pre_better (the order k_preempt_pick applies over the tiles), the candidate counts summed.
+// kg_pre_better (a node with no victim, then the fewest PDB-violating victims, then the rest) (the order k_preempt_pick applies over the tiles), the candidate counts summed.
 kg_status kg_preempt_merge(const int64_t *picks, int32_t n_lists, int32_t n, int64_t *out) {
     if (n_lists < 1 || n < 0 || !picks || !out) return KG_ERR_INVALID_ARG;
     constexpr int W = KG_PREEMPT_PICK_WORDS;
@@ -966,7 +1031,9 @@ kg_status kg_preempt_merge(const int64_t *picks, int32_t n_lists, int32_t n, int
         for (int32_t l = 0; l < n_lists; l++) {
             const int64_t *c = picks + ((size_t)l * (size_t)n + (size_t)p) * W;
             cands += c[7];
-            if (kg_pre_better(c[0], c[1], c[2], c[3], c[4], best[0], best[1], best[2], best[3], best[4]))
+            // word 1: n_victims | n_violating << 32
+            if (kg_pre_better(c[0], c[1] >> 32, c[1] & 0xFFFFFFFFll, c[2], c[3], c[4], best[0], best[1] >> 32,
+                              best[1] & 0xFFFFFFFFll, best[2], best[3], best[4]))
                 for (int w = 0; w < W; w++) best[w] = c[w];
         }
         best[7] = best[0] < 0 ? 0 : cands;

@@ -113,6 +113,56 @@ def row_preempt(cfg: np.ndarray, node_row: np.ndarray, bound_rows: np.ndarray, b
             "hi_prio": int(stats[1]), "prio_sum": int(stats[2]), "earliest_ns": int(stats[3])}
 
 
+def row_preempt_pdb(cfg: np.ndarray, node_row: np.ndarray, bound_rows: np.ndarray, bound_priority, bound_start_ns,
+                    bound_pdb_prio, pod_row: np.ndarray, pod_priority: int, now_ns: int,
+                    quotas: Optional[np.ndarray] = None) -> dict:
+    """kg_row_preempt_pdb: row_preempt with one PDB threshold per bound pod (pdb_thresholds; None: the plain form).
+    Adds n_violating (numViolatingVictim) to row_preempt's result."""
+    rows = np.ascontiguousarray(bound_rows, dtype=nat.POD_ROW).reshape(-1)
+    n = len(rows)
+    pr = np.ascontiguousarray(bound_priority, dtype=np.int32).reshape(-1)
+    ts = np.ascontiguousarray(bound_start_ns, dtype=np.int64).reshape(-1)
+    th = None if bound_pdb_prio is None else np.ascontiguousarray(bound_pdb_prio, dtype=np.int32).reshape(-1)
+    if len(pr) != n or len(ts) != n or (th is not None and len(th) != n):
+        raise ValueError("row_preempt_pdb takes one priority, one start time and one threshold per bound row")
+    q = None if quotas is None else np.ascontiguousarray(quotas, dtype=nat.QUOTA).reshape(-1)
+    status = ctypes.c_int32(0)
+    mask = np.zeros(2, dtype=np.uint64)
+    stats = np.zeros(5, dtype=np.int64)
+    if th is not None and n == 0:
+        th = np.zeros(1, dtype=np.int32)   # (a non-null pointer: an empty list still runs the PDB form)
+    _check(nat.lib().kg_row_preempt_pdb(nat.ptr(cfg), nat.ptr(node_row), nat.ptr(rows) if n else None,
+                                        nat.ptr(pr) if n else None, nat.ptr(ts) if n else None,
+                                        nat.ptr(th) if th is not None else None, n, nat.ptr(pod_row), int(pod_priority),
+                                        nat.ptr(q) if q is not None and len(q) else None, 0 if q is None else len(q),
+                                        int(now_ns), ctypes.byref(status), nat.ptr(mask), nat.ptr(stats)),
+           what="kg_row_preempt_pdb")
+    return {"status": int(status.value), "victims": unpack_victims(mask), "n_victims": int(stats[0]),
+            "hi_prio": int(stats[1]), "prio_sum": int(stats[2]), "earliest_ns": int(stats[3]), "n_violating": int(stats[4])}
+
+
+def pdb_thresholds(priority, start_ns, quota, non_preemptible, pdb_first, pdb_ids, allowed) -> np.ndarray:
+    """kg_pdb_thresholds: the PDB thresholds of one node's bound list (caller order).  Pod b decrements the PDBs
+    pdb_ids[pdb_first[b]:pdb_first[b + 1]] (indices into `allowed`, the PDBs' Status.DisruptionsAllowed).  Returns
+    int32 [n]: pod b is PDB-violating for a preemptor of priority P  <=>  out[b] < P (nat.PDB_PRIO_NONE: never)."""
+    pr = np.ascontiguousarray(priority, dtype=np.int32).reshape(-1)
+    n = len(pr)
+    ts = np.ascontiguousarray(start_ns, dtype=np.int64).reshape(-1)
+    qg = np.ascontiguousarray(quota, dtype=np.int32).reshape(-1)
+    npre = np.ascontiguousarray(non_preemptible, dtype=np.uint8).reshape(-1)
+    pf = np.ascontiguousarray(pdb_first, dtype=np.int32).reshape(-1)
+    ids = np.ascontiguousarray(pdb_ids, dtype=np.int32).reshape(-1)
+    al = np.ascontiguousarray(allowed, dtype=np.int32).reshape(-1)
+    if len(ts) != n or len(qg) != n or len(npre) != n or len(pf) != n + 1:
+        raise ValueError("pdb_thresholds takes one start time, quota and flag per pod and n + 1 offsets")
+    out = np.zeros(n, dtype=np.int32)
+    _check(nat.lib().kg_pdb_thresholds(nat.ptr(pr) if n else None, nat.ptr(ts) if n else None, nat.ptr(qg) if n else None,
+                                       nat.ptr(npre) if n else None, n, nat.ptr(pf), nat.ptr(ids) if len(ids) else None,
+                                       nat.ptr(al) if len(al) else None, len(al), nat.ptr(out) if n else None),
+           what="kg_pdb_thresholds")
+    return out
+
+
 def unpack_victims(words: np.ndarray) -> np.ndarray:
     """Victim mask words uint64 [..., 2] -> bool [..., nat.BOUND_MAX_PER_NODE] (bit b: position b of the node's list)."""
     w = np.ascontiguousarray(words, dtype=np.uint64)
@@ -121,10 +171,11 @@ def unpack_victims(words: np.ndarray) -> np.ndarray:
 
 
 def _pick_dict(pick: np.ndarray) -> dict:
-    """kg_preempt's pick words int64 [n][8] as named arrays."""
+    """kg_preempt's pick words int64 [n][8] as named arrays (word 1: n_victims | n_violating << 32)."""
     pick = np.ascontiguousarray(pick, dtype=np.int64).reshape(-1, nat.PREEMPT_PICK_WORDS)
     return {"node": pick[:, 0].astype(np.int32), "victims": unpack_victims(pick[:, 5:7].view(np.uint64)),
-            "n_victims": pick[:, 1].astype(np.int32), "hi_prio": pick[:, 2].astype(np.int32), "prio_sum": pick[:, 3].copy(),
+            "n_victims": (pick[:, 1] & 0xFFFFFFFF).astype(np.int32), "n_violating": (pick[:, 1] >> 32).astype(np.int32),
+            "hi_prio": pick[:, 2].astype(np.int32), "prio_sum": pick[:, 3].copy(),
             "earliest_ns": pick[:, 4].copy(), "n_candidates": pick[:, 7].astype(np.int32), "pick": pick}
 
 
@@ -688,13 +739,48 @@ class Engine:
                                            ctypes.byref(n)), self, "kg_bound_download")
         return rows[:n.value].copy(), pr[:n.value].copy(), ts[:n.value].copy()
 
+    def set_bound_pdb(self, first, pdb_prio) -> None:
+        """kg_bound_pdb_set: load the PDB threshold plane (pdb_thresholds / ingest.bound_pdb), one int32 per bound pod in
+        set_bound_pods' order with the same `first`; pdb_prio None drops the plane (preempt() then answers without
+        PDBs again).  set_bound_pods and load_snapshot drop it too."""
+        if pdb_prio is None:
+            _check(nat.lib().kg_bound_pdb_set(self._h, None, None), self, "kg_bound_pdb_set")
+            return
+        first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        if len(first) != self.n_nodes + 1:
+            raise ValueError("set_bound_pdb takes n_nodes + 1 offsets")
+        th = np.ascontiguousarray(pdb_prio, dtype=np.int32).reshape(-1)
+        if len(th) != int(first[-1]):
+            raise ValueError("set_bound_pdb takes one threshold per bound pod")
+        if not len(th):
+            th = np.zeros(1, dtype=np.int32)   # (a non-null pointer: an all-empty table still gets a plane)
+        _check(nat.lib().kg_bound_pdb_set(self._h, nat.ptr(first), nat.ptr(th)), self, "kg_bound_pdb_set")
+
+    def update_bound_pdb(self, node: int, pdb_prio) -> None:
+        """kg_bound_pdb_update: replace one node's thresholds (as many as its list holds).  update_bound_pods resets the
+        node's values to nat.PDB_PRIO_NONE; this call follows it."""
+        th = np.ascontiguousarray(pdb_prio, dtype=np.int32).reshape(-1)
+        n = len(th)
+        _check(nat.lib().kg_bound_pdb_update(self._h, int(node), nat.ptr(th) if n else None, n), self, "kg_bound_pdb_update")
+
+    def download_bound_pdb(self, node: int) -> np.ndarray:
+        """kg_bound_pdb_download: one node's thresholds in the caller's order."""
+        cap = int(getattr(self, "bound_max", nat.BOUND_MAX_PER_NODE))
+        out = np.zeros(cap, dtype=np.int32)
+        n = ctypes.c_int32(0)
+        _check(nat.lib().kg_bound_pdb_download(self._h, int(node), nat.ptr(out), cap, ctypes.byref(n)), self,
+               "kg_bound_pdb_download")
+        return out[:n.value].copy()
+
     def preempt(self, pod_rows: np.ndarray, priority, now_ns: int, plane: bool = False) -> dict:
         """kg_preempt: the preemption dry run of the pods (at most nat.PREEMPT_MAX_PODS rows with their priorities; they
         travel with the call, the batch of set_pods is not touched) against every node of the shard, and the node to
         preempt on.  Returns node [n] i32 (-1: no candidate), victims [n][128] bool (positions in the picked node's
         list), n_victims, hi_prio, prio_sum, earliest_ns, n_candidates and pick (the raw words, for merge_preempt);
-        with `plane` also status / n_victims_plane / n_potential [n][stride] (columns as eval()'s planes).  Mutates
-        nothing."""
+        with `plane` also status / n_victims_plane / n_potential [n][stride] (columns as eval()'s planes).  With a PDB
+        threshold plane loaded (set_bound_pdb) the violating potential victims are reprieved first and n_violating /
+        n_violating_plane hold numViolatingVictim, the pick's criterion after "no victim"; both are zero without one.
+        Mutates nothing."""
         rows = np.ascontiguousarray(pod_rows, dtype=nat.POD_ROW).reshape(-1)
         n = len(rows)
         pr = np.ascontiguousarray(priority, dtype=np.int32).reshape(-1)
@@ -710,6 +796,7 @@ class Engine:
             res["status"] = (cells & np.uint32(0xFF)).astype(np.uint8)
             res["n_victims_plane"] = ((cells >> np.uint32(8)) & np.uint32(0xFF)).astype(np.uint8)
             res["n_potential"] = ((cells >> np.uint32(16)) & np.uint32(0xFF)).astype(np.uint8)
+            res["n_violating_plane"] = (cells >> np.uint32(24)).astype(np.uint8)
             res["plane"] = cells
         return res
 

@@ -31,7 +31,7 @@ import json
 import math
 import re
 from fractions import Fraction
-from typing import Dict, Iterable, List, Optional, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 from . import objects as ob
 from .objects import parse_quantity
@@ -565,6 +565,20 @@ def cluster_from_objects(nodes: Iterable[dict], pods: Iterable[dict] = (), node_
     return cl
 
 
+def _bound_lists(cluster: ob.Cluster):
+    """The bound pods of every node in bound_pods' order, and the CSR offsets over cluster.nodes."""
+    import numpy as np
+
+    by_node: Dict[str, List[ob.Pod]] = {}
+    for p in cluster.lister_pods.values():
+        if p.node_name and not p.terminated:
+            by_node.setdefault(p.node_name, []).append(p)
+    flat = [p for n in cluster.nodes for p in by_node.get(n.name, [])]
+    first = np.zeros(len(cluster.nodes) + 1, dtype=np.int32)
+    first[1:] = np.cumsum([len(by_node.get(n.name, [])) for n in cluster.nodes])
+    return flat, first
+
+
 def bound_pods(cfg, cluster: ob.Cluster):
     """The bound-pod table of a cluster for Engine.set_bound_pods (NodeInfo.Pods of every node as the preemption dry
     run reads it): (first, rows, priority, start_ns) - CSR offsets over cluster.nodes, the pod rows, PodPriority
@@ -574,15 +588,75 @@ def bound_pods(cfg, cluster: ob.Cluster):
 
     from . import _native as nat
     from . import engine
-    by_node: Dict[str, List[ob.Pod]] = {}
-    for p in cluster.lister_pods.values():
-        if p.node_name and not p.terminated:
-            by_node.setdefault(p.node_name, []).append(p)
-    flat = [p for n in cluster.nodes for p in by_node.get(n.name, [])]
-    first = np.zeros(len(cluster.nodes) + 1, dtype=np.int32)
-    first[1:] = np.cumsum([len(by_node.get(n.name, [])) for n in cluster.nodes])
+    flat, first = _bound_lists(cluster)
     view = cluster.view()
     rows = engine.build_pod_rows(cfg, view, [view.pod_index(p) for p in flat])
     priority = np.array([p.priority or 0 for p in flat], dtype=np.int32)
     start_ns = np.array([nat.START_NS_NONE if p.start_time_ns is None else p.start_time_ns for p in flat], dtype=np.int64)
     return first, rows, priority, start_ns
+
+
+def _selector_matches(selector, labels: Dict[str, str]):
+    """metav1.LabelSelectorAsSelector(selector).Matches(labels) for a k8s-shaped dict; None when the reference skips
+    the PDB: a nil or empty selector (it matches nothing) or one that does not convert (an unknown operator, In / NotIn
+    without values, Exists / DoesNotExist with values)."""
+    if not selector:
+        return None
+    match_labels = selector.get("matchLabels") or {}
+    exprs = selector.get("matchExpressions") or []
+    if not match_labels and not exprs:
+        return None
+    ok = all(labels.get(k) == v and k in labels for k, v in match_labels.items())
+    for e in exprs:
+        key, op, values = e.get("key"), e.get("operator"), list(e.get("values") or [])
+        if op in ("In", "NotIn"):
+            if not values:
+                return None
+            inside = key in labels and labels[key] in values
+            ok = ok and (inside if op == "In" else not inside)
+        elif op in ("Exists", "DoesNotExist"):
+            if values:
+                return None
+            ok = ok and ((key in labels) == (op == "Exists"))
+        else:
+            return None
+    return ok
+
+
+def bound_pdb(cfg, cluster: ob.Cluster, pdbs: Sequence[dict]):
+    """The PDB thresholds of a cluster's bound pods for Engine.set_bound_pdb: int32, parallel to bound_pods' rows.
+    `pdbs`: k8s-shaped PodDisruptionBudget dicts (metadata.namespace, spec.selector with matchLabels /
+    matchExpressions, status.disruptionsAllowed, status.disruptedPods).  A PDB decrements for a pod as in
+    filterPodsWithPDBViolation (elasticquota/preempt.go:217-267): same namespace, a non-empty selector that matches the
+    pod's labels, the pod's name not in status.disruptedPods; a pod without labels matches none."""
+    import numpy as np
+
+    from . import _native as nat
+    from . import engine
+    flat, first = _bound_lists(cluster)
+    _, rows, priority, start_ns = bound_pods(cfg, cluster)
+    allowed = np.array([int((d.get("status") or {}).get("disruptionsAllowed") or 0) for d in pdbs], dtype=np.int32)
+    ids: List[List[int]] = []
+    for p in flat:
+        mine: List[int] = []
+        if p.labels:
+            for i, d in enumerate(pdbs):
+                if ((d.get("metadata") or {}).get("namespace") or "default") != p.namespace:
+                    continue
+                if not _selector_matches((d.get("spec") or {}).get("selector"), p.labels):
+                    continue
+                if p.name in ((d.get("status") or {}).get("disruptedPods") or {}):
+                    continue
+                mine.append(i)
+        ids.append(mine)
+    out = np.full(len(flat), nat.PDB_PRIO_NONE, dtype=np.int32)
+    for j in range(len(cluster.nodes)):
+        lo, hi = int(first[j]), int(first[j + 1])
+        if hi == lo:
+            continue
+        pf = np.zeros(hi - lo + 1, dtype=np.int32)
+        pf[1:] = np.cumsum([len(x) for x in ids[lo:hi]])
+        out[lo:hi] = engine.pdb_thresholds(priority[lo:hi], start_ns[lo:hi], rows["quota"][lo:hi],
+                                           (rows["flags"][lo:hi] & nat.POD_NON_PREEMPTIBLE) != 0, pf,
+                                           [i for x in ids[lo:hi] for i in x], allowed)
+    return out
