@@ -35,6 +35,10 @@
  *                           (reservation/plugin.go:552-574, frameworkext/reservation_info.go:390-401), ElasticQuota
  *                           GroupQuotaManager.UnreservePod (elasticquota/plugin.go:339-351,
  *                           core/group_quota_manager.go:799-805), and NodeInfo.RemovePod of ForgetPod
+ *   kg_place_gangs          kg_place with Coscheduling's Strict-mode rejection inside the batch: a gang member without
+ *   / kg_gang_plan          a node rejects its gang group (coscheduling/core/core.go:276-306, :362-388), the members
+ *                           already reserved are Unreserved (:343-360) and the rest fail PreFilter (:255-269); the
+ *                           verdict per gang is the caller's Permit decision (gang.go:480-495)
  *   kg_cycle_one            one pass of upstream scheduleOne for one pod in one launch: Filter + Score over every
  *                           node, selectHost, and (KG_CYCLE_COMMIT) the Reserve of the chosen node
  *   kg_candidates           upstream numFeasibleNodesToFind + prioritizeNodes over the engine's plugins: per pod the K
@@ -899,6 +903,61 @@ kg_status kg_unreserve(kg_engine *eng, const kg_pod_row *pods, const int32_t *no
                        const int64_t *zone_release /* [n][KG_MAX_ZONES][2] or NULL */,
                        const int32_t *rsv_slot     /* [n], kg_rsv_set index or -1; or NULL */,
                        uint8_t *released           /* [n] out, host */);
+
+/* Gang-aware placement: kg_place over the uploaded batch with Coscheduling's all-or-nothing rejection applied inside
+ * the batch.  pod_gang[p] names the gang of pod p (-1: none, a plain pod; pass -1 too for a once-satisfied gang or one
+ * the caller does not want enforced); gang_min[g] is max(0, MinRequiredNumber - members already waiting or bound
+ * outside this batch) (the caller's reading of isGangValidForPermit, gang.go:480-495); gang_group[g] is the gang
+ * group of g as an index in [0, n_gangs) (NULL: every gang is its own group); gang_flags[g] is KG_GANG_STRICT
+ * (extension.GangModeStrict) or 0.  PodGroup bookkeeping, timeouts and match policies stay with the caller.
+ * For each pod p in queue order, with g = pod_gang[p], G its group and rejected[G] false at the start:
+ *  1. g strict and rejected[G]: out_node[p] = out_score[p] = -1; the pod is not evaluated and leaves no trace on rows,
+ *     planes or quota state (PreFilter of an invalid schedule cycle, coscheduling/core/core.go:255-269).
+ *  2. Otherwise one cycle exactly as kg_place runs it on the snapshot of that moment (eligibility classes, spill
+ *     pods, the ElasticQuota gate on the current `used`, the lowest node index on ties, the Reserve).
+ *  3. The cycle finds no node (for any reason, the quota gate included) and g is strict: rejected[G] is set and every
+ *     earlier pod q < p of a gang of G with out_node[q] >= 0 is unreserved exactly as kg_unreserve(pods[q],
+ *     out_node[q]) would (row, every derived plane, ElasticQuota used / non_preemptible_used up the parent chain) and
+ *     gets out_node[q] = out_score[q] = -1 (rejectGangGroupById, core.go:276-306, :343-388).  All of this is complete
+ *     before pod p + 1's cycle: the reference rejects the waiting pods asynchronously, "before the next pod" is this
+ *     engine's deterministic rule.
+ *  4. A non-strict member without a node is simply unschedulable (core.go:305).
+ *  5. After the last pod, gang g is satisfied iff its pods with out_node >= 0 number at least gang_min[g];
+ *     out_verdict[g] is its group's verdict: KG_GANG_REJECTED if rejected[G], else KG_GANG_ALLOWED if every gang of G
+ *     is satisfied, else KG_GANG_WAITING (its Reserves stay: the pods wait in Permit).  With
+ *     KG_PLACE_GANG_RELEASE_WAITING the WAITING groups, strict or not, are rolled back as in rule 3 (the Permit
+ *     timeout); their verdict stays KG_GANG_WAITING.
+ *  6. n_gangs = 0, or every pod_gang = -1, gives exactly kg_place.  Results do not depend on kg_config.place_chunk
+ *     or kg_set_forms: a gang batch always takes the sequential chunk loop, with chunks cut as kg_gang_plan reports.
+ * Errors (nothing launched, nothing changed): KG_ERR_INVALID_ARG for a null pod_gang / out_node / out_score with pods
+ * uploaded, a null gang_min / gang_flags / out_verdict with n_gangs > 0, n_gangs < 0, unknown flags or gang_flags
+ * bits, a negative gang_min, or gangs of one group that disagree on KG_GANG_STRICT; KG_ERR_RANGE for a pod_gang outside
+ * [-1, n_gangs) or a gang_group outside [0, n_gangs); KG_ERR_STATE as kg_place (no snapshot, a stale engine, a shard
+ * set, a quota index without a group); KG_ERR_UNSUPPORTED with KG_PLUGIN_NUMA enabled (the release needs the recorded
+ * zone allocations and cpusets) or Reservation enabled with slots loaded (it needs the nominated slot).
+ * kg_counters.placed grows by the pods with out_node >= 0 at return; the generation moves as in kg_place (once per
+ * resolved chunk), so it is unchanged exactly when nothing was launched. */
+#define KG_GANG_STRICT 0x1u /* gang_flags */
+#define KG_GANG_ALLOWED 0   /* out_verdict */
+#define KG_GANG_WAITING 1
+#define KG_GANG_REJECTED 2
+#define KG_PLACE_GANG_RELEASE_WAITING 0x1u /* flags */
+kg_status kg_place_gangs(kg_engine *eng, int64_t now_ns,
+                         const int32_t *pod_gang   /* [P] gang index of each pod of the uploaded batch, -1: none */,
+                         const int32_t *gang_min   /* [n_gangs] members this batch must still place for Permit */,
+                         const int32_t *gang_group /* [n_gangs] gang-group index in [0, n_gangs); NULL: gang g is group g */,
+                         const uint8_t *gang_flags /* [n_gangs] KG_GANG_STRICT or 0 */,
+                         int32_t n_gangs, uint32_t flags,
+                         int32_t *out_node, int64_t *out_score /* [P], as kg_place */,
+                         uint8_t *out_verdict /* [n_gangs] */);
+
+/* Host only, no engine: the argument checks above that need no engine (pod_gang, gang_group, gang_flags, n_gangs;
+ * n_pods < 0 or a null cut with n_pods > 0: KG_ERR_INVALID_ARG) and the chunk cuts kg_place_gangs will use for
+ * place_chunk = chunk (<= 0: the default 16; clamped to KG_PLACE_CHUNK_MAX): cut[p] = 1 when a placement chunk ends
+ * after pod p.  A chunk is at most `chunk` consecutive pods that are all members of one strict gang group or hold
+ * no strict-gang pod.  On an error cut is untouched. */
+kg_status kg_gang_plan(const int32_t *pod_gang, int32_t n_pods, const int32_t *gang_group, const uint8_t *gang_flags,
+                       int32_t n_gangs, int32_t chunk, uint8_t *cut /* [n_pods] */);
 
 /* One scheduling cycle of one pod (upstream scheduleOne: Filter and Score over every node of the shard,
  * selectHost, Reserve) as ONE kernel launch and ONE stream synchronisation: the per-pod loop of the Go plugins

@@ -67,6 +67,10 @@ DIAG_FIRST_FAIL = 0x1
 WHY_SLOTS, WHY_SLOT_REJECTED, WHY_SLOT_FEASIBLE = 32, 30, 31
 DIAG_MAX_PODS = 256
 UNRESERVE_MAX = 4096   # KG_UNRESERVE_MAX: entries of one kg_unreserve call
+# gang-aware placement (kg_place_gangs): gang_flags, the verdicts, the call flag
+GANG_STRICT = 0x1
+GANG_ALLOWED, GANG_WAITING, GANG_REJECTED = range(3)
+PLACE_GANG_RELEASE_WAITING = 0x1
 CAND_MAX_K = 64          # KG_CAND_MAX_K: longest kg_candidates list
 CAND_MAX_PODS = 256      # KG_CAND_MAX_PODS: pods of one kg_candidates call
 # preemption dry run (kg_row_preempt / kg_preempt): the per-pair status, the table and call limits, the pick layout
@@ -263,7 +267,7 @@ EXPORTED = [
     "kg_pods_restricted_count", "kg_row_why", "kg_diagnose", "kg_row_unreserve", "kg_row_numa_alloc", "kg_unreserve",
     "kg_candidates", "kg_candidates_merge", "kg_bound_set", "kg_bound_update", "kg_bound_download", "kg_row_preempt",
     "kg_preempt", "kg_preempt_merge", "kg_pdb_thresholds", "kg_bound_pdb_set", "kg_bound_pdb_update",
-    "kg_bound_pdb_download", "kg_row_preempt_pdb",
+    "kg_bound_pdb_download", "kg_row_preempt_pdb", "kg_place_gangs", "kg_gang_plan",
 ]
 
 _lib = None
@@ -333,6 +337,8 @@ def lib() -> ctypes.CDLL:
         "kg_bound_pdb_set": (i32, [vp, vp, vp]), "kg_bound_pdb_update": (i32, [vp, i32, vp, i32]),
         "kg_bound_pdb_download": (i32, [vp, i32, vp, i32, vp]),
         "kg_row_preempt_pdb": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i64, vp, vp, vp]),
+        "kg_place_gangs": (i32, [vp, i64, vp, vp, vp, vp, i32, ctypes.c_uint32, vp, vp, vp]),
+        "kg_gang_plan": (i32, [vp, i32, vp, vp, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         if host_only and not hasattr(L, name):

@@ -94,6 +94,8 @@
 //   140-141 k_bound_update            staged record (read), bound table slot and node
 //   142     k_preempt (PDB forms)     threshold plane slot and node (read)
 //   143-144 k_bound_pdb_fill          staged thresholds (read), threshold plane slot and node
+//   145-149 k_gang_settle             group of a gang (closed / release words), gang of a pod (counts), pod, node (row
+//                                     and planes), quota group of a chain
 #ifdef KG_BOUNDS_CHECK
 __device__ unsigned long long g_kg_oob[4];   // count, first site, first index, first bound
 __device__ __noinline__ bool kg_oob_ok(int site, int64_t idx, int64_t bound) {
@@ -2226,6 +2228,9 @@ struct RsvArgs {
     int32_t *Mn;                // [pods] their count
     unsigned long long *G;      // [pods][ngroups] per 64-entry group: the best key of its other feasible entries
     int32_t ngroups;
+    // kg_place_gangs, a chunk of one strict gang group: the group's `closed` word (nullptr in every other launch).
+    // Non-zero: the group was rejected, its pods are not evaluated; the resolve sets it where a pod finds no node.
+    int32_t *closed;
 };
 #define KG_RSV_GROUP 64
 #define KG_RSV_MAX_GROUPS 2048   // the resolve's touched-group flags (LDS): up to 131072 reservation nodes
@@ -2854,7 +2859,9 @@ __global__ __launch_bounds__(KG_RESOLVE_THREADS) void k_resolve(kg_consts c, kg_
         const int par = j & 1;
         const kg_pod_dev &pd = lpod[par];
         if (tid == 0)  // ElasticQuota PreFilter on the quota state after every earlier Reserve (read after the sync below)
-            gate_ok[par] = !ra.quota || pd.quota < 0 || kg_quota_pass(ra.quota, pd.quota, pd, ra.quota_parent != 0);
+            // (a strict gang chunk: a pod of a rejected group is not scheduled either; this thread wrote the word)
+            gate_ok[par] = !(ra.closed && *ra.closed) &&
+                           (!ra.quota || pd.quota < 0 || kg_quota_pass(ra.quota, pd.quota, pd, ra.quota_parent != 0));
         // prefetch pod j + 1 (its slot's last reader, pod j − 1, is past this pod's first barrier... see the
         // note above: a barrier-free pod j − 1 reads its row only before its own second barrier)
         if (j + 1 < n && tid >= KG_RESOLVE_THREADS - POD_DW)
@@ -3029,6 +3036,7 @@ __global__ __launch_bounds__(KG_RESOLVE_THREADS) void k_resolve(kg_consts c, kg_
             if (tid == 0) {
                 out_node[j] = node;
                 out_score[j] = w ? (int64_t)(w >> 32) - 1 : -1;
+                if (ra.closed && node < 0) *ra.closed = 1;   // a strict gang member without a node rejects its group
             }
             if (rsv_on && ra.M && j + 1 < n && tid >= KG_RESOLVE_THREADS / 2)   // (the reduction's reads are done)
                 rsv_prefetch(ra, j + 1, rpf, tid - KG_RESOLVE_THREADS / 2, KG_RESOLVE_THREADS / 2);
@@ -3458,6 +3466,169 @@ __global__ __launch_bounds__(64) void k_unreserve_quota(kg_quota *qs, int32_t n_
             }
         }
         __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// kg_place_gangs: the rollback of a rejected (or timed-out) gang group inside a placement batch
+// ---------------------------------------------------------------------------------------
+// Launched on the engine stream behind a strict chunk's k_resolve (grp = the chunk's group: a no-op unless the
+// resolve set the group's closed word) and once after the last chunk for KG_PLACE_GANG_RELEASE_WAITING (grp = -1: the
+// kernel first counts every gang's placed pods, marks the groups holding a gang below its gang_min, and releases
+// those).  One 64-thread workgroup walks the batch's pods [0, end) in queue order and undoes the Reserve of each
+// placed pod of a marked group, one pod at a time, so several members on one node need no grouping and no atomics
+// on rows: the k_unreserve parts for a single entry on the staged row (lanes as there, without the zone and
+// reservation parts: kg_place_gangs refuses both), the planes and flags re-derived by the same kg_finalize_*
+// functions, the quota release of k_unreserve_quota by one lane (kg_rl_sub_pod up the chain), then −1 to both
+// outputs.  The workgroup barriers order one pod's row and plane stores before the next pod's reads.
+// A release returns a node to a state it had earlier in the call, so the slow-node list stays a superset of the
+// slow nodes (the host rebuilds it after the call).
+struct GangArgs {
+    const kg_pod_dev *pods;     // the uploaded batch
+    const int32_t *pod_gang;    // [n_pods] gang of each pod, −1: none
+    const int32_t *gang_group;  // [n_gangs] group of each gang
+    const int32_t *gang_min;    // [n_gangs]
+    int32_t *mark;              // [n_gangs] per group: the closed words (grp ≥ 0) or the release marks (grp < 0)
+    int32_t *count;             // [n_gangs] placed pods per gang (grp < 0)
+    int32_t *out_node;          // [n_pods]
+    int64_t *out_score;         // [n_pods]
+    kg_quota *quota;            // nullptr: ElasticQuota off
+    int32_t n_pods, n_gangs, n_quota, n_nodes;
+    int32_t grp, end;
+};
+// one kg_place_gangs call, as place_loop reads it
+struct GangRun {
+    const int32_t *pod_gang, *gang_group, *gang_min;   // the caller's arrays (gang_group may be null)
+    const uint8_t *gang_flags;
+    int32_t n_gangs;
+    bool release;                      // KG_PLACE_GANG_RELEASE_WAITING
+    std::vector<uint8_t> cut;          // [P] kg_gang_plan's cuts for the engine's chunk
+    std::vector<int32_t> strict_grp;   // [P] the group of a strict gang's pod, −1 for every other pod
+    std::vector<int32_t> group;        // [n_gangs] the group of each gang (gang_group, or the identity)
+    int32_t *closed = nullptr, *rel = nullptr, *count = nullptr;   // device words, [n_gangs] each (after the upload)
+};
+
+__global__ __launch_bounds__(64) void k_gang_settle(kg_consts c, kg_planes pl, GangArgs a) {
+    constexpr int ROW_U4 = (int)(sizeof(kg_node_row) / 16);
+    static_assert(sizeof(kg_node_row) % 16 == 0 && ROW_U4 <= 64, "rows are staged as 16-byte words by one wave");
+    __shared__ __attribute__((aligned(16))) kg_node_row srow;
+    __shared__ uint32_t fin[2 * KG_NUM_RES];
+    __shared__ uint32_t fl_over[3], fl_pods_full;
+    const int tid = threadIdx.x;
+    if (a.grp >= 0) {
+        if (!KG_IN(145, a.grp, a.n_gangs) || !a.mark[a.grp]) return;   // (uniform)
+    } else {
+        for (int32_t g = tid; g < a.n_gangs; g += 64) {
+            a.count[g] = 0;
+            a.mark[g] = 0;
+        }
+        __syncthreads();
+        for (int32_t p = tid; p < a.n_pods; p += 64) {
+            const int32_t g = a.pod_gang[p];
+            if (g >= 0 && KG_IN(146, g, a.n_gangs) && a.out_node[p] >= 0) atomicAdd(&a.count[g], 1);
+        }
+        __syncthreads();
+        for (int32_t g = tid; g < a.n_gangs; g += 64) {
+            const int32_t have = __hip_atomic_load(&a.count[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int32_t gr = a.gang_group[g];
+            if (have < a.gang_min[g] && KG_IN(145, gr, a.n_gangs))
+                __hip_atomic_store(&a.mark[gr], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+    }
+    const int32_t end = a.end < a.n_pods ? a.end : a.n_pods;
+    for (int32_t base = 0; base < end; base += 64) {
+        const int32_t p = base + tid;
+        bool need = false;
+        if (p < end) {
+            const int32_t g = a.pod_gang[p];
+            if (g >= 0 && KG_IN(146, g, a.n_gangs) && a.out_node[p] >= 0) {
+                const int32_t gr = a.gang_group[g];
+                if (a.grp >= 0) need = gr == a.grp;
+                else if (KG_IN(145, gr, a.n_gangs)) need = __hip_atomic_load(&a.mark[gr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+            }
+        }
+        unsigned long long todo = __ballot(need);
+        while (todo) {   // (uniform)
+            const int32_t q = base + (int32_t)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            if (!KG_IN(147, q, a.n_pods)) continue;
+            const int32_t node = a.out_node[q];
+            if (!KG_IN(148, node, a.n_nodes)) continue;
+            const kg_pod_dev &pd = a.pods[q];
+            if (tid < ROW_U4) reinterpret_cast<uint4 *>(&srow)[tid] = reinterpret_cast<const uint4 *>(pl.rows + node)[tid];
+            __syncthreads();
+            kg_node_row &row = pl.rows[node];
+            if (tid < KG_NUM_RES) {
+                const int r = tid;
+                const int64_t req = (int64_t)((uint64_t)srow.requested[r] - (uint64_t)pd.req[r]);
+                srow.requested[r] = req;
+                row.requested[r] = req;
+                if (r < 2) {
+                    const int64_t nz = (int64_t)((uint64_t)srow.nonzero_requested[r] - (uint64_t)pd.nonzero[r]);
+                    srow.nonzero_requested[r] = nz;
+                    row.nonzero_requested[r] = nz;
+                }
+                if (r < 3) fl_over[r] = srow.alloc[r] - req < 0 ? 1u : 0u;
+                fin[r] = kg_finalize_fit_r(c, pl, node, srow, r);
+            } else if (tid < KG_UNR_LAX0) {
+                const int r = tid - KG_UNR_LA0;
+                const uint64_t est = (uint64_t)pd.la_est_i[r];
+                const int64_t u0 = (int64_t)((uint64_t)srow.la_used[0][r] - est);
+                const int64_t u1 = (int64_t)((uint64_t)srow.la_used[1][r] - ((pd.flags & KG_POD_PROD) ? est : 0ull));
+                srow.la_used[0][r] = u0;
+                srow.la_used[1][r] = u1;
+                row.la_used[0][r] = u0;
+                row.la_used[1][r] = u1;
+                fin[KG_UNR_LA0 + r] = kg_finalize_la_r(c, pl, node, srow, r);
+            } else if (tid < KG_UNR_ZONE0) {
+                const int x = tid - KG_UNR_LAX0;
+                const uint64_t est = (uint64_t)pd.la_est_x[x];
+                const int64_t u0 = (int64_t)((uint64_t)srow.la_used_x[0][x] - est);
+                const int64_t u1 = (int64_t)((uint64_t)srow.la_used_x[1][x] - ((pd.flags & KG_POD_PROD) ? est : 0ull));
+                srow.la_used_x[0][x] = u0;
+                srow.la_used_x[1][x] = u1;
+                row.la_used_x[0][x] = u0;
+                row.la_used_x[1][x] = u1;
+                fin[KG_UNR_LAX0 + x] = c.la_extra && kg_finalize_lax_r(c, pl, node, srow, x) ? 1u : 0u;
+            } else if (tid == KG_UNR_PODS) {
+                const int32_t pc = srow.pod_count - 1;
+                row.pod_count = pc;
+                fl_pods_full = (int64_t)pc + 1 > (int64_t)srow.allowed_pods ? 1u : 0u;
+            } else if (tid == 63) {   // GroupQuotaManager.UnreservePod: the pod's group and every ancestor
+                if (a.quota && pd.quota >= 0) {
+                    for (int32_t g = pd.quota, d = 0; g >= 0 && d <= KG_QUOTA_MAX_DEPTH; d++) {
+                        if (!KG_IN(149, g, a.n_quota)) break;
+                        kg_rl_sub_pod(a.quota[g].used, pd);
+                        if (pd.flags & KG_POD_NON_PREEMPTIBLE) kg_rl_sub_pod(a.quota[g].non_preemptible_used, pd);
+                        g = a.quota[g].parent;
+                    }
+                }
+                a.out_node[q] = -1;
+                a.out_score[q] = -1;
+            }
+            __syncthreads();
+            if (tid == 0) {   // kg_finalize_flags from the parts (metric and the static bits are unchanged)
+                bool slow = false, xslow = false;
+                uint32_t fmask = 0;
+                for (int r = 0; r < KG_NUM_RES; r++) slow = slow || (fin[r] & 1u);
+                xslow = slow;
+                for (int r = KG_UNR_LA0; r < KG_UNR_LAX0; r++) {
+                    slow = slow || (fin[r] & 1u);
+                    xslow = xslow || (fin[r] & 2u);
+                }
+                for (int x = 0; x < KG_NUM_RES - 2; x++) xslow = xslow || (fin[KG_UNR_LAX0 + x] & 1u);
+                for (int r = 0; r < KG_NUM_RES; r++)
+                    if (fin[r] & 2u) fmask |= 1u << r;
+                const bool over[3] = {fl_over[0] != 0, fl_over[1] != 0, fl_over[2] != 0};
+                const uint32_t old = pl.dflags[node];
+                uint32_t dyn = kg_dflags_dynamic(fl_pods_full != 0, over, slow, xslow);
+                if (old & KGD_RSV) dyn &= ~(KGD_SLOW | KGD_XSLOW);   // kg_rsv_pair owns reservation nodes
+                pl.dflags[node] = (old & ~KGD_DYNAMIC) | dyn;
+                pl.fit_mask[node] = fmask;
+            }
+            __syncthreads();   // the row, planes and flags of this pod before the next one stages its node
+        }
     }
 }
 
@@ -4435,6 +4606,11 @@ struct kg_engine {
     size_t unr_bytes = 0, unr_host_bytes = 0;
     std::vector<uint8_t> node_zones;
     std::vector<int32_t> rsv_inv;
+    // kg_place_gangs: the call's gang run (nullptr outside it: place_loop is kg_place's) and its device block
+    // (pod_gang, gang_group, gang_min, then the closed / release / count words; grown on demand)
+    GangRun *gang = nullptr;
+    void *gang_mem = nullptr;
+    size_t gang_bytes = 0;
     int32_t comm_rank = 0, comm_world = 0;
     hipStream_t eval_stream = nullptr;  // kg_set_eval_stream (kg_place_chunk_eval), nullptr ⇒ stream
     // recorded on eval_stream after each kg_place_chunk_eval, one per partial buffer (keyed by its address): a chunk
@@ -5470,6 +5646,7 @@ void kg_engine_destroy(kg_engine *e) {
     if (e->pre_host) (void)hipHostFree(e->pre_host);
     if (e->unr_mem) (void)hipFree(e->unr_mem);
     if (e->unr_host) (void)hipHostFree(e->unr_host);
+    if (e->gang_mem) (void)hipFree(e->gang_mem);
     if (e->hot_lax) (void)hipFree(e->hot_lax);
     if (e->eq_pods) (void)hipFree(e->eq_pods);
     if (e->eq_perm) (void)hipFree(e->eq_perm);
@@ -6259,7 +6436,7 @@ kg_status chunk_eval(kg_engine *e, int64_t now_ns, int32_t pod_begin, int32_t n,
 kg_status chunk_resolve(kg_engine *e, int64_t now_ns, int32_t pod_begin, int32_t n, const uint32_t *partial_dev,
                         int32_t *out_node_dev, int64_t *out_score_dev, bool defer_last,
                         const int32_t *prev_nodes_dev = nullptr, int32_t n_prev = 0,
-                        unsigned long long *pvkeys = nullptr) {
+                        unsigned long long *pvkeys = nullptr, int32_t *closed = nullptr) {
     if (pod_begin < 0 || n < 0 || n > KG_MAX_CHUNK || pod_begin + (int64_t)n > e->n_pods)
         return set_err(e, KG_ERR_RANGE, "bad chunk");
     if (n == 0) return KG_OK;
@@ -6267,6 +6444,7 @@ kg_status chunk_resolve(kg_engine *e, int64_t now_ns, int32_t pod_begin, int32_t
     if (st) return st;
     e->ctr.resolved += (uint64_t)n;
     RsvArgs ra = rsv_args(e);
+    ra.closed = closed;   // (kg_place_gangs: a chunk of one strict gang group)
     if (ra.rsv) {  // this chunk's entries were written by kg_place_chunk_eval from row 0
         if (n > KG_RSV_POD_CHUNK) return set_err(e, KG_ERR_RANGE, "chunk larger than the reservation entry buffer");
     }
@@ -6816,6 +6994,45 @@ kg_status merge_verdict(kg_engine *e, const uint32_t *part, int32_t n) {
     return KG_OK;
 }
 
+// kg_place_gangs: the run's device block — pod_gang, the gangs' groups and minimums uploaded, the closed words zeroed
+kg_status gang_upload(kg_engine *e, GangRun &gr, GangArgs &ga) {
+    const size_t P = (size_t)e->n_pods, ng = (size_t)gr.n_gangs;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t pg_b = up(4 * P), g_b = up(4 * (ng ? ng : 1));
+    const size_t need = pg_b + 5 * g_b;
+    if (e->gang_bytes < need) {
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (e->gang_mem) HIP_TRY(e, hipFree(e->gang_mem));
+        e->gang_mem = nullptr;
+        e->gang_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->gang_mem, need));
+        e->gang_bytes = need;
+    }
+    char *m = (char *)e->gang_mem;
+    int32_t *d_pg = (int32_t *)m, *d_grp = (int32_t *)(m + pg_b), *d_min = (int32_t *)(m + pg_b + g_b);
+    gr.closed = (int32_t *)(m + pg_b + 2 * g_b);
+    gr.rel = (int32_t *)(m + pg_b + 3 * g_b);
+    gr.count = (int32_t *)(m + pg_b + 4 * g_b);
+    // (the sources outlive the call's last stream synchronisation: the caller's arrays and the run's own)
+    HIP_TRY(e, h2d(e, d_pg, gr.pod_gang, 4 * P, e->stream));
+    if (ng) {
+        HIP_TRY(e, h2d(e, d_grp, gr.group.data(), 4 * ng, e->stream));
+        HIP_TRY(e, h2d(e, d_min, gr.gang_min, 4 * ng, e->stream));
+    }
+    HIP_TRY(e, hipMemsetAsync(gr.closed, 0, 2 * g_b, e->stream));   // closed and release words
+    ga.pods = e->pods;
+    ga.pod_gang = d_pg;
+    ga.gang_group = d_grp;
+    ga.gang_min = d_min;
+    ga.count = gr.count;
+    ga.quota = rsv_args(e).quota;
+    ga.n_pods = e->n_pods;
+    ga.n_gangs = gr.n_gangs;
+    ga.n_quota = e->n_quota;
+    ga.n_nodes = (int32_t)e->n_nodes;
+    return KG_OK;
+}
+
 // the ranks agree that every one of them is ready for the chunk loop (one all-reduce of a status flag after each
 // rank's own allocations and checks): a rank that failed returns its error, the others KG_ERR_STATE, none enters
 // the loop, so no rank waits in a collective its peer never issues
@@ -6855,7 +7072,8 @@ kg_status place_loop(kg_engine *e, int64_t now_ns, int32_t *out_node, int64_t *o
     const uint8_t may_mask = e->n_node_bind_nodes > 0 ? 3 : 1;
     // the pipeline pays two cross-stream event hops per chunk: it wins where the chunk evaluation is long
     // (NodeNUMAResource: config 3 5.0k → 6.1k pods/s) and loses where it is short (config 2: 82k → 61k)
-    const bool pipelined = !bind_mode && !rsv_args(e).rsv && !(e->forms & KG_FORM_PLACE_SEQUENTIAL) &&
+    // (a gang batch never: a rollback changes nodes that are not in the previous chunk's list)
+    const bool pipelined = !e->gang && !bind_mode && !rsv_args(e).rsv && !(e->forms & KG_FORM_PLACE_SEQUENTIAL) &&
                            ((e->forms & KG_FORM_PLACE_PIPELINE) || (e->consts.plugins & KG_PLUGIN_NUMA));
     if (!st) st = quota_ready(e);   // (before the pipeline: chunk_resolve checks it too, with an evaluation in flight)
     if (!st) st = elig_ready(e);
@@ -6871,10 +7089,18 @@ kg_status place_loop(kg_engine *e, int64_t now_ns, int32_t *out_node, int64_t *o
     st = ensure_scratch(e, head + up(part_b) + up((size_t)P * 4) + up((size_t)P * 8) + 256);
     if (sharded) st = comm_agree(e, st);
     if (st) return st;
+    GangRun *gr = e->gang;
+    GangArgs ga{};
+    if (gr) {
+        st = gang_upload(e, *gr, ga);
+        if (st) return st;
+    }
     char *s = (char *)e->scratch + head;
     uint32_t *part = (uint32_t *)s;
     int32_t *dnode = (int32_t *)(s + up(part_b));
     int64_t *dscore = (int64_t *)(s + up(part_b) + up((size_t)P * 4));
+    ga.out_node = dnode;
+    ga.out_score = dscore;
     // the placement kernels answer cpusets on NUMA-policy nodes for this batch (kg_consts.numa_bz)
     struct BzScope {
         kg_consts &k;
@@ -6895,6 +7121,15 @@ kg_status place_loop(kg_engine *e, int64_t now_ns, int32_t *out_node, int64_t *o
                     defer = true;
                     break;
                 }
+        int32_t sgrp = -1;   // kg_place_gangs: the chunk ends at kg_gang_plan's cut; its strict group, if it is one's
+        if (gr) {
+            for (int32_t k = 0; k < n; k++)
+                if (gr->cut[(size_t)(b + k)]) {
+                    n = k + 1;
+                    break;
+                }
+            sgrp = gr->strict_grp[(size_t)b];
+        }
         last_n = n;
         if (!local) {
             st = chunk_eval(e, now_ns, b, n, part);
@@ -6911,10 +7146,18 @@ kg_status place_loop(kg_engine *e, int64_t now_ns, int32_t *out_node, int64_t *o
             }
         }
         if (!local) {
-            st = chunk_resolve(e, now_ns, b, n, part, dnode + b, dscore + b, defer);
+            st = chunk_resolve(e, now_ns, b, n, part, dnode + b, dscore + b, defer, nullptr, 0, nullptr,
+                               sgrp >= 0 ? gr->closed + sgrp : nullptr);
             if (st) {
                 if (!sharded) return st;
                 local = st;
+            }
+            if (sgrp >= 0) {   // the group's rollback, if the resolve closed it, before the next chunk's evaluation
+                ga.mark = gr->closed;
+                ga.grp = sgrp;
+                ga.end = b + n;
+                hipLaunchKernelGGL(k_gang_settle, dim3(1), dim3(64), 0, e->stream, e->consts, e->pl, ga);
+                HIP_TRY(e, hipGetLastError());
             }
         }
         if (defer && !local) {
@@ -6946,10 +7189,99 @@ kg_status place_loop(kg_engine *e, int64_t now_ns, int32_t *out_node, int64_t *o
         e->stale = true;   // the replicas stopped at different chunks
         return local;
     }
+    if (gr) {
+        if (gr->release) {   // the Permit timeout: every group still holding an unsatisfied gang is rolled back
+            ga.mark = gr->rel;
+            ga.grp = -1;
+            ga.end = P;
+            hipLaunchKernelGGL(k_gang_settle, dim3(1), dim3(64), 0, e->stream, e->consts, e->pl, ga);
+            HIP_TRY(e, hipGetLastError());
+        }
+        e->slow_valid = false;   // a release can move a node across the fp64 bounds (kg_unreserve's rule)
+    }
     HIP_TRY(e, hipMemcpyAsync(out_node, dnode, (size_t)P * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipMemcpyAsync(out_score, dscore, (size_t)P * 8, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     if (sharded) return merge_verdict(e, part, last_n);
+    return KG_OK;
+}
+
+// kg_place with Coscheduling's Strict-mode rejection inside the batch (koord_gpu.h): the argument checks and chunk
+// cuts of kg_gang_plan, place_loop's sequential chunk loop with the group's closed word in each strict chunk's
+// resolve and k_gang_settle behind it, then the verdicts from the downloaded placements and words.
+kg_status kg_place_gangs(kg_engine *e, int64_t now_ns, const int32_t *pod_gang, const int32_t *gang_min,
+                         const int32_t *gang_group, const uint8_t *gang_flags, int32_t n_gangs, uint32_t flags,
+                         int32_t *out_node, int64_t *out_score, uint8_t *out_verdict) {
+    kg_status st = check_engine(e);
+    if (st) return st;
+    const int32_t P = e->n_pods;
+    if (flags & ~KG_PLACE_GANG_RELEASE_WAITING) return set_err(e, KG_ERR_INVALID_ARG, "unknown kg_place_gangs flags 0x%x", flags);
+    if (n_gangs < 0) return set_err(e, KG_ERR_INVALID_ARG, "n_gangs < 0");
+    if (P > 0 && (!pod_gang || !out_node || !out_score)) return set_err(e, KG_ERR_INVALID_ARG, "null pod_gang or outputs");
+    if (n_gangs > 0 && (!gang_min || !gang_flags || !out_verdict))
+        return set_err(e, KG_ERR_INVALID_ARG, "null gang_min, gang_flags or out_verdict");
+    for (int32_t g = 0; g < n_gangs; g++)
+        if (gang_min[g] < 0) return set_err(e, KG_ERR_INVALID_ARG, "gang %d: negative gang_min", g);
+    int32_t chunk = e->cfg.place_chunk > 0 ? e->cfg.place_chunk : 16;
+    if (chunk > KG_MAX_CHUNK) chunk = KG_MAX_CHUNK;
+    GangRun gr;
+    gr.cut.assign((size_t)P, 0);
+    st = kg_gang_plan(pod_gang, P, gang_group, gang_flags, n_gangs, chunk, gr.cut.data());
+    if (st == KG_ERR_RANGE) return set_err(e, st, "a pod_gang outside [-1, %d) or a gang_group outside [0, %d)", n_gangs, n_gangs);
+    if (st) return set_err(e, st, "unknown gang_flags bits, or gangs of one group that disagree on KG_GANG_STRICT");
+    if (!e->plane_mem) return set_err(e, KG_ERR_STATE, "snapshot not initialised");
+    if (e->shard_begin != 0 || e->shard_end != e->n_nodes)
+        return set_err(e, KG_ERR_STATE, "kg_place_gangs runs on the whole snapshot");
+    // what the rollback does not release
+    const uint32_t plug = e->cfg.enabled_plugins;
+    if (plug & KG_PLUGIN_NUMA)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_place_gangs under NodeNUMAResource (the release needs the recorded zone "
+                                              "allocations and cpusets)");
+    if ((plug & KG_PLUGIN_RESERVATION) && e->n_rn > 0)
+        return set_err(e, KG_ERR_UNSUPPORTED, "kg_place_gangs with reservation slots loaded (the release needs the nominated slot)");
+    gr.pod_gang = pod_gang;
+    gr.gang_group = gang_group;
+    gr.gang_min = gang_min;
+    gr.gang_flags = gang_flags;
+    gr.n_gangs = n_gangs;
+    gr.release = (flags & KG_PLACE_GANG_RELEASE_WAITING) != 0;
+    gr.group.resize((size_t)n_gangs);
+    for (int32_t g = 0; g < n_gangs; g++) gr.group[(size_t)g] = gang_group ? gang_group[g] : g;
+    gr.strict_grp.assign((size_t)P, -1);
+    bool any = false;
+    for (int32_t p = 0; p < P; p++)
+        if (pod_gang[p] >= 0) {
+            any = true;
+            if (gang_flags[pod_gang[p]] & KG_GANG_STRICT) gr.strict_grp[(size_t)p] = gr.group[(size_t)pod_gang[p]];
+        }
+    const uint64_t resolved0 = e->ctr.resolved;
+    // no gang member in the batch: kg_place itself (its pipeline included); the verdicts follow from gang_min alone
+    e->gang = any ? &gr : nullptr;
+    st = place_loop(e, now_ns, out_node, out_score, false);
+    e->gang = nullptr;
+    std::vector<int32_t> words((size_t)n_gangs * 2, 0);   // closed, release
+    if (st == KG_OK && any && n_gangs > 0) {
+        HIP_TRY(e, hipMemcpyAsync(words.data(), gr.closed, 4 * (size_t)n_gangs, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipMemcpyAsync(words.data() + n_gangs, gr.rel, 4 * (size_t)n_gangs, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+    }
+    if (st == KG_OK) st = bounds_verdict(e);
+    if (st) return st;
+    e->ctr.resolved = resolved0 + (uint64_t)P;
+    for (int32_t p = 0; p < P; p++) e->ctr.placed += out_node[p] >= 0 ? 1u : 0u;
+    // rule 5: a group holding an unsatisfied gang waits (with the release its pods are gone by now: the device's marks)
+    std::vector<int32_t> have((size_t)n_gangs, 0);
+    for (int32_t p = 0; p < P; p++)
+        if (pod_gang[p] >= 0 && out_node[p] >= 0) have[(size_t)pod_gang[p]]++;
+    std::vector<uint8_t> waiting((size_t)n_gangs, 0);
+    for (int32_t g = 0; g < n_gangs; g++) {
+        const size_t G = (size_t)gr.group[(size_t)g];
+        if (gr.release && any ? words[(size_t)n_gangs + G] != 0 : have[(size_t)g] < gang_min[g]) waiting[G] = 1;
+    }
+    for (int32_t g = 0; g < n_gangs; g++) {
+        const size_t G = (size_t)gr.group[(size_t)g];
+        out_verdict[g] = words[G] ? KG_GANG_REJECTED : waiting[G] ? KG_GANG_WAITING : KG_GANG_ALLOWED;
+    }
     return KG_OK;
 }
 

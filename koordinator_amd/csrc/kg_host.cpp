@@ -1291,3 +1291,41 @@ extern "C" kg_status kg_candidates_merge(const uint64_t *keys, const uint8_t *sc
         }
     return KG_OK;
 }
+
+// kg_gang_plan (koord_gpu.h): the argument checks kg_place_gangs shares and the chunk cuts its loop takes.  A chunk
+// is a run of at most `chunk` consecutive pods that are either all members of one strict gang group or hold no
+// strict-gang pod, so every pod behind a failing strict pod in its chunk belongs to the failing group.
+extern "C" kg_status kg_gang_plan(const int32_t *pod_gang, int32_t n_pods, const int32_t *gang_group,
+                                  const uint8_t *gang_flags, int32_t n_gangs, int32_t chunk, uint8_t *cut) {
+    if (n_pods < 0 || n_gangs < 0) return KG_ERR_INVALID_ARG;
+    if (n_pods > 0 && (!pod_gang || !cut)) return KG_ERR_INVALID_ARG;
+    if (n_gangs > 0 && !gang_flags) return KG_ERR_INVALID_ARG;
+    for (int32_t g = 0; g < n_gangs; g++)
+        if (gang_flags[g] & ~KG_GANG_STRICT) return KG_ERR_INVALID_ARG;
+    for (int32_t g = 0; g < n_gangs; g++)
+        if (gang_group && (gang_group[g] < 0 || gang_group[g] >= n_gangs)) return KG_ERR_RANGE;
+    for (int32_t p = 0; p < n_pods; p++)
+        if (pod_gang[p] < -1 || pod_gang[p] >= n_gangs) return KG_ERR_RANGE;
+    // the gangs of one group agree on the mode (the group's first gang sets it)
+    std::vector<int8_t> mode((size_t)n_gangs, -1);
+    for (int32_t g = 0; g < n_gangs; g++) {
+        int8_t &m = mode[(size_t)(gang_group ? gang_group[g] : g)];
+        const int8_t strict = (gang_flags[g] & KG_GANG_STRICT) ? 1 : 0;
+        if (m >= 0 && m != strict) return KG_ERR_INVALID_ARG;
+        m = strict;
+    }
+    if (chunk <= 0) chunk = 16;   // kg_config.place_chunk's default and limit
+    if (chunk > KG_PLACE_CHUNK_MAX) chunk = KG_PLACE_CHUNK_MAX;
+    auto strict_group = [&](int32_t p) {
+        const int32_t g = pod_gang[p];
+        if (g < 0 || !(gang_flags[g] & KG_GANG_STRICT)) return (int32_t)-1;
+        return gang_group ? gang_group[g] : g;
+    };
+    int32_t len = 0;
+    for (int32_t p = 0; p < n_pods; p++) {
+        len++;
+        cut[p] = (p + 1 == n_pods || len == chunk || strict_group(p + 1) != strict_group(p)) ? 1 : 0;
+        if (cut[p]) len = 0;
+    }
+    return KG_OK;
+}

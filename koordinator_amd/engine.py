@@ -49,6 +49,21 @@ def row_unreserve(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray, zo
            what="kg_row_unreserve")
 
 
+def gang_plan(pod_gang, gang_flags, gang_group=None, chunk: int = 0) -> np.ndarray:
+    """kg_gang_plan: the argument checks of Engine.place_gangs that need no engine and the chunk cuts it will use for
+    place_chunk = `chunk` (0: the default 16).  Returns uint8 [P]: 1 where a placement chunk ends after the pod."""
+    pg = np.ascontiguousarray(pod_gang, dtype=np.int32).reshape(-1)
+    gf = np.ascontiguousarray(gang_flags, dtype=np.uint8).reshape(-1)
+    gg = None if gang_group is None else np.ascontiguousarray(gang_group, dtype=np.int32).reshape(-1)
+    if gg is not None and len(gg) != len(gf):
+        raise ValueError("gang_flags and gang_group describe the same gangs")
+    cut = np.zeros(len(pg), dtype=np.uint8)
+    _check(nat.lib().kg_gang_plan(nat.ptr(pg) if len(pg) else None, len(pg), nat.ptr(gg) if len(gf) else None,
+                                  nat.ptr(gf) if len(gf) else None, len(gf), int(chunk), nat.ptr(cut) if len(pg) else None),
+           what="kg_gang_plan")
+    return cut
+
+
 def row_numa_alloc(cfg: np.ndarray, node_row: np.ndarray, pod_row: np.ndarray) -> np.ndarray:
     """kg_row_numa_alloc: the zone amounts row_commit would record for the pod on this (pre-Reserve) row, int64
     [MAX_ZONES][2] by zone slot; all zero where the commit records nothing.  The row is not modified."""
@@ -523,6 +538,32 @@ class Engine:
         scores = np.zeros(P, dtype=np.int64)
         _check(nat.lib().kg_place(self._h, int(now_ns), nat.ptr(nodes), nat.ptr(scores)), self, "kg_place")
         return nodes, scores
+
+    def place_gangs(self, now_ns: int, pod_gang, gang_min, gang_flags, gang_group=None, release_waiting: bool = False):
+        """kg_place_gangs: place() with Coscheduling's Strict-mode rejection inside the batch.  `pod_gang`: int32 [P], the
+        gang of each pod of the uploaded batch (-1: none); `gang_min`: int32 [n_gangs], the members the batch must
+        still place; `gang_flags`: uint8 [n_gangs], nat.GANG_STRICT or 0; `gang_group`: int32 [n_gangs] or None (every
+        gang its own group); `release_waiting`: roll the WAITING groups back (the Permit timeout).  Returns
+        (nodes, scores, verdicts): verdicts uint8 [n_gangs] of nat.GANG_ALLOWED / GANG_WAITING / GANG_REJECTED."""
+        P = self.n_pods
+        pg = np.ascontiguousarray(pod_gang, dtype=np.int32).reshape(-1)
+        if len(pg) != P:
+            raise ValueError("place_gangs takes one gang index per pod of the batch")
+        gm = np.ascontiguousarray(gang_min, dtype=np.int32).reshape(-1)
+        gf = np.ascontiguousarray(gang_flags, dtype=np.uint8).reshape(-1)
+        ng = len(gm)
+        gg = None if gang_group is None else np.ascontiguousarray(gang_group, dtype=np.int32).reshape(-1)
+        if len(gf) != ng or (gg is not None and len(gg) != ng):
+            raise ValueError("gang_min, gang_flags and gang_group describe the same gangs")
+        nodes = np.zeros(P, dtype=np.int32)
+        scores = np.zeros(P, dtype=np.int64)
+        verdicts = np.zeros(ng, dtype=np.uint8)
+        _check(nat.lib().kg_place_gangs(self._h, int(now_ns), nat.ptr(pg) if P else None, nat.ptr(gm) if ng else None,
+                                        nat.ptr(gg) if ng else None, nat.ptr(gf) if ng else None, ng,
+                                        nat.PLACE_GANG_RELEASE_WAITING if release_waiting else 0,
+                                        nat.ptr(nodes) if P else None, nat.ptr(scores) if P else None,
+                                        nat.ptr(verdicts) if ng else None), self, "kg_place_gangs")
+        return nodes, scores, verdicts
 
     def chunk_eval(self, now_ns: int, pod_begin: int, n: int, partial_ptr: int) -> None:
         _check(nat.lib().kg_place_chunk_eval(self._h, int(now_ns), pod_begin, n, ctypes.c_void_p(partial_ptr)), self,
